@@ -2,6 +2,8 @@
 """Depth Anything V2 throughput on MI355X through the HIP engine.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--encoder vits]
+    python bench.py --full [...]                      (every leg below as well)
+    python bench.py --dump-outputs DIR [...]          (the last timed step's outputs)
     python bench.py --gpus 8 --encoder vitl --global-batch 8   (BASELINE config 3)
     python bench.py --model depth_pro [--batch 4]     (SURVEY.md 8f row 3, 1536^2)
     python bench.py --model vggt [--batch 8] [--frames 1]   (SURVEY.md 8f row 4, 518^2)
@@ -20,7 +22,16 @@ per GPU); `--global-batch G` shards G images over the ranks instead (strong
 scaling, replicas.shard: config 3 = ViT-L, G = 8).  VGGT counts frames: a
 batch item of S frames is S images.
 
-Also measured (rank 0):
+A plain run does only that: it sets up, warms up, times the K steps, writes
+the outputs when asked and prints the result line (metric, value, unit,
+ms_per_step, ...; the fields of the legs below are null or absent).
+`--dump-outputs DIR` writes what the last timed step left in the output
+tensors as DIR/<name>.npy (float32; rank r > 0 of a multi-GPU run writes
+DIR/<name>_rank<r>.npy).  The inputs are seeded, so two builds run with the
+same arguments are comparable output for output.  Above 64 MB in all, each
+array is a fixed seeded sample of its flattened elements (DUMP_SEED).
+
+With `--full`, also measured (rank 0, except the PCIe leg and output_finite):
   * b1_*: the reference's own methodology (core/bench.py:182-210): batch 1,
     wall clock of one do_inference() = pinned H2D + forward + D2H + sync,
     20 warmup / 100 iterations, with the StageTimer split -- the number to
@@ -114,11 +125,20 @@ def parse_size(v: str):
 REF_SIZE_MS = {(392, 518): 3.7605, (518, 518): 4.2852, (672, 896): 10.4632}
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: most it writes over all arrays
+DUMP_SEED = 20240607        # ... and the seed of the sample when the outputs are larger
+
+
 def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: PCIe-inclusive stream, per-layer profile + "
+                        "roofline, batch-1 reference method, CPU baseline, output finiteness check")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
     p.add_argument("--model", default="depth_anything_v2", choices=["depth_anything_v2", "depth_pro", "vggt"])
     p.add_argument("--batch", type=int, default=0,
                    help="batch items per GPU per step (default 48; depth_pro 4; vggt 8)")
@@ -140,8 +160,30 @@ def parse(argv=None):
                    help="allow more ranks than visible GPUs (a launcher rehearsal: ranks share devices round-robin; "
                         "the line is marked devices_shared and its scaling field is not a scaling measurement)")
     p.add_argument("--profile-iters", type=int, default=3)
-    p.add_argument("--layers-json", default="", help="write the per-layer profile here (rank 0)")
-    return p.parse_args(argv)
+    p.add_argument("--layers-json", default="", help="write the per-layer profile here (rank 0; needs --full)")
+    a = p.parse_args(argv)
+    if a.layers_json and not a.full:
+        p.error("--layers-json writes the per-layer profile, which only a --full run takes")
+    return a
+
+
+def dump_outputs(outs, directory, rank=0):
+    """Write the output tensors as DIR/<name>.npy (float32).  Within DUMP_BYTES
+    in all they are written whole; beyond it each array becomes a 1-D sample of
+    its flattened elements at sorted indices drawn once from DUMP_SEED (the
+    same indices in every run of the same shapes)."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    total = sum(t.numel() for t in outs.values())
+    keep = DUMP_BYTES // 4
+    for i, (name, t) in enumerate(sorted(outs.items())):
+        t = t.detach().float()
+        if total > keep:
+            n = max(1, keep * t.numel() // total)
+            idx = np.sort(np.random.default_rng(DUMP_SEED + i).integers(0, t.numel(), n))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        fn = f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"
+        np.save(os.path.join(directory, fn), t.cpu().numpy())
 
 
 class LayerTimes:
@@ -568,8 +610,10 @@ def main():
                                dist.barrier if dist is not None else None)
     per_rank = replicas.gather_to_rank0(round(el, 6))
     el = replicas.max_over_ranks(el)
+    if a.dump_outputs and B > 0:
+        dump_outputs(wl.y, a.dump_outputs, rank)
     pcie = None
-    if not a.no_pcie:
+    if a.full and not a.no_pcie:
         if ctx is not None:
             el_p, b_in, b_out = pcie_streamed_region(wl, ctx, st, a.steps, a.warmup, torch.cuda.synchronize,
                                                      dist.barrier if dist is not None else None)
@@ -583,7 +627,9 @@ def main():
                 "pcie_method": "pinned host batch -> H2D -> forward (graph) -> D2H into pinned host; forward stream + "
                                "one copy stream, double-buffered device I/O, H2D(i+1) and D2H(i-1) under forward(i); "
                                "wall clock over K steps bracketed by barrier + device sync, max over ranks"}
-    out_ok = all(bool(torch.isfinite(t).all().item()) for t in wl.y.values()) if B > 0 else True
+    out_ok = None
+    if a.full:
+        out_ok = all(bool(torch.isfinite(t).all().item()) for t in wl.y.values()) if B > 0 else True
     value = total_items * wl.frames * a.steps / el
     ms_step = el / a.steps * 1e3
 
@@ -596,28 +642,30 @@ def main():
             dist.destroy_process_group()
         return
 
-    layer_ms = profile_layers(ctx, sh, a.profile_iters)
-    tfile = traffic_path(a.model, wl.encoder, B, S, wl.frames)
-    roof, breakdown = roofline(wl.cfg, B, S, layer_ms, wl.frames, tfile)
-    if roof["traffic"] is None:
-        log(f"no committed PMC profile covers '{roof['kernel']}' at this workload "
-            f"({os.path.relpath(tfile, ROOT)}): roofline.traffic is null -- "
-            f"bash tools/profile_round.sh <out> {' '.join(sys.argv[1:])}")
-    if a.layers_json:
-        with open(a.layers_json, "w") as f:
-            json.dump({"batch": B, "frames": wl.frames, "layer_ms": layer_ms, "classes": breakdown, "roofline": roof},
-                      f, indent=1)
+    roof, breakdown = None, {}
+    if a.full:
+        layer_ms = profile_layers(ctx, sh, a.profile_iters)
+        tfile = traffic_path(a.model, wl.encoder, B, S, wl.frames)
+        roof, breakdown = roofline(wl.cfg, B, S, layer_ms, wl.frames, tfile)
+        if roof["traffic"] is None:
+            log(f"no committed PMC profile covers '{roof['kernel']}' at this workload "
+                f"({os.path.relpath(tfile, ROOT)}): roofline.traffic is null -- "
+                f"bash tools/profile_round.sh <out> {' '.join(sys.argv[1:])}")
+        if a.layers_json:
+            with open(a.layers_json, "w") as f:
+                json.dump({"batch": B, "frames": wl.frames, "layer_ms": layer_ms, "classes": breakdown,
+                           "roofline": roof}, f, indent=1)
     # MFMA fraction of the whole job: every GPU's share of the work at the job's rate
     model_frac = value / world * wl.gflop * 1e9 / (MFMA_PEAK_TFLOPS * 1e12)
     ctx.destroy()
     eng.destroy()
-    res_b1 = {} if a.no_b1 else wl.b1_legs(a, local)
+    res_b1 = wl.b1_legs(a, local) if a.full and not a.no_b1 else {}
     if "b1_compute_ms" in res_b1:
         # batch-1 forward (the engine compute of one image, hipEvent-timed inside do_inference)
         res_b1["b1_model_mfma_frac"] = round(wl.gflop * 1e9 / (res_b1["b1_compute_ms"] * 1e-3) /
                                              (MFMA_PEAK_TFLOPS * 1e12), 4)
     cpu = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # N > 1: the other ranks are done and wait at the closing barrier
         cpu = cpu_baseline(wl.cfg, S, a.cpu_seconds)
     for c, v in list(breakdown.items())[:10]:

@@ -78,6 +78,36 @@ def test_bench_self_launches(monkeypatch):
                     "argv": ["--gpus", "2", "--encoder", "vitl", "--global-batch", "8"]}
 
 
+def test_bench_plain_and_full_options():
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d", "--layers-json", "l.json"])
+    assert a.full and a.dump_outputs == "d"
+    with pytest.raises(SystemExit):          # the per-layer profile is a --full leg
+        bench.parse(["--layers-json", "l.json"])
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    outs = {"depth": torch.arange(2 * 5 * 7, dtype=torch.float32).reshape(2, 5, 7), "fov": torch.tensor([1.5, 2.5])}
+    bench.dump_outputs(outs, str(tmp_path / "whole"))
+    d = np.load(tmp_path / "whole" / "depth.npy")
+    assert d.dtype == np.float32 and np.array_equal(d, outs["depth"].numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "fov.npy"), [1.5, 2.5])
+    # over the byte budget: a fixed seeded sample, the same in every run, within the budget
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 36)
+    got = []
+    for run in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / run), rank=1)
+        got.append({n: np.load(tmp_path / run / f"{n}_rank1.npy") for n in outs})
+    assert all(np.array_equal(got[0][n], got[1][n]) for n in outs)
+    assert sum(v.nbytes for v in got[0].values()) <= 4 * 36 and got[0]["depth"].size == 35
+    assert set(got[0]["depth"].tolist()) <= set(range(70)) and got[0]["depth"].dtype == np.float32
+
+
 def test_bench_rank_work():
     import bench
     a = bench.parse(["--encoder", "vitl", "--global-batch", "8"])

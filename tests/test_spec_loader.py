@@ -9,7 +9,9 @@ import pytest
 
 from monocular_depth_estimation_trt_amd import spec
 
-REF_SPEC = "/root/reference/models/depth_anything_v2/spec.json"
+# the reference's own spec.json files, stored unchanged (settings only)
+REF_SPECS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_specs")
+REF_SPEC = os.path.join(REF_SPECS, "depth_anything_v2.json")
 
 
 def test_shipped_spec():
@@ -33,14 +35,10 @@ def test_family_specs(name, post):
 
 @pytest.mark.parametrize("name", ["depth_anything_ac", "distill_any_depth"])
 def test_reference_family_specs_load_unchanged(name):
-    p = f"/root/reference/models/{name}/spec.json"
-    if not os.path.exists(p):
-        pytest.skip("reference checkout not present")
-    mc = spec.model_config_of(spec.load(p))
+    mc = spec.model_config_of(spec.load(os.path.join(REF_SPECS, f"{name}.json")))
     assert mc["encoder"] == "vits" and mc["depth_type"] == "relative"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SPEC), reason="reference checkout not present")
 def test_reference_spec_loads_unchanged():
     s = spec.load(REF_SPEC)
     assert spec.size_of(s) == (518, 518) and s["encoder"]["used"] == "vits"

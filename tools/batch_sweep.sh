@@ -11,7 +11,7 @@ mkdir -p "$O"
 run() {  # tag, args...
   local tag=$1; shift
   echo "[sweep $(date +%T)] $tag $*"
-  timeout -k 10 300 python -u bench.py --steps "$K" --warmup 5 --no-b1 --no-cpu-baseline --no-pcie \
+  timeout -k 10 300 python -u bench.py --full --steps "$K" --warmup 5 --no-b1 --no-cpu-baseline --no-pcie \
     --profile-iters 1 "$@" > "$O/$tag.json" 2> "$O/$tag.err" || { echo "[sweep] $tag rc=$?"; tail -5 "$O/$tag.err"; exit 1; }
 }
 for b in 1 2 4 8 16 32 48 64; do run "vits_b$b" --encoder vits --batch "$b"; done

@@ -52,11 +52,11 @@ for t in "$@"; do
     profile)
       bash tools/profile_round.sh "$O/prof_$tag" "${args[@]}" || { log "profile rc=$?"; exit 1; } ;;
     pmc)
-      bash tools/pmc_profile.sh "$O/pmc_$tag" -- python3 bench.py --steps 3 --warmup 1 --no-b1 --no-cpu-baseline \
+      bash tools/pmc_profile.sh "$O/pmc_$tag" -- python3 bench.py --full --steps 3 --warmup 1 --no-b1 --no-cpu-baseline \
         --no-pcie --profile-iters 1 "${args[@]}" || { log "pmc rc=$?"; exit 1; } ;;
     trace)
       timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$O/trace_$tag" -o tr -- \
-        python3 bench.py --no-b1 --no-cpu-baseline --profile-iters 1 "${args[@]}" > "$O/trace_$tag.log" 2>&1 \
+        python3 bench.py --full --no-b1 --no-cpu-baseline --profile-iters 1 "${args[@]}" > "$O/trace_$tag.log" 2>&1 \
         || { log "trace rc=$?"; tail -20 "$O/trace_$tag.log"; exit 1; } ;;
     kpmc)
       bash tools/pmc_profile.sh "$O/kpmc_$tag" -- python3 tools/bench_kernels.py --iters 3 "${args[@]}" \

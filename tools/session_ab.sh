@@ -5,5 +5,5 @@ set -o pipefail
 O=$1; K=$2; OFF=$3; shift 3
 A=$(IFS=,; echo "$*")
 bash tools/gpu_tasks.sh $O "tests:$K" \
-  bench:on:--no-cpu-baseline${A:+,$A} env:$OFF bench:off:--no-cpu-baseline${A:+,$A} unenv:${OFF%%=*} \
-  bench:on2:--no-cpu-baseline${A:+,$A}
+  bench:on:--full,--no-cpu-baseline${A:+,$A} env:$OFF bench:off:--full,--no-cpu-baseline${A:+,$A} unenv:${OFF%%=*} \
+  bench:on2:--full,--no-cpu-baseline${A:+,$A}

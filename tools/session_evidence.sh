@@ -7,12 +7,12 @@
 set -o pipefail
 O=${1:-gpurun_out/ev}
 bash tools/gpu_tasks.sh $O tests smoke \
-  bench:def: \
+  bench:def:--full \
   profile:def \
   pmc:def: \
-  bench:vitl1:--encoder,vitl,--batch,1,--no-cpu-baseline,--no-pcie \
-  bench:fp32:--precision,fp32,--batch,8,--no-cpu-baseline,--no-pcie \
-  bench:s392:--size,392x518,--no-cpu-baseline,--no-pcie \
-  bench:s672:--size,672x896,--no-cpu-baseline,--no-pcie \
-  bench:dp:--model,depth_pro,--no-cpu-baseline,--no-pcie \
-  bench:vggt:--model,vggt,--no-cpu-baseline,--no-pcie
+  bench:vitl1:--full,--encoder,vitl,--batch,1,--no-cpu-baseline,--no-pcie \
+  bench:fp32:--full,--precision,fp32,--batch,8,--no-cpu-baseline,--no-pcie \
+  bench:s392:--full,--size,392x518,--no-cpu-baseline,--no-pcie \
+  bench:s672:--full,--size,672x896,--no-cpu-baseline,--no-pcie \
+  bench:dp:--full,--model,depth_pro,--no-cpu-baseline,--no-pcie \
+  bench:vggt:--full,--model,vggt,--no-cpu-baseline,--no-pcie
