@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MDE_ABI_VERSION 8
+#define MDE_ABI_VERSION 9
 
 typedef enum {
   MDE_OK = 0,
@@ -288,6 +288,43 @@ int mde_op_patch_prep_u8(const unsigned char* img_u8, int batch, int h, int w, f
  * align_corners=True resize of fp32 depth [batch][ih][iw] to [batch][oh][ow], then clamp to [lo, hi]. */
 int mde_op_depth_postprocess(const float* depth, int batch, int ih, int iw, float* out, int oh, int ow, float lo,
                              float hi, void* stream);
+/* Pre-process (since ABI 9; reference core/preprocess.py:preprocess_for for the stretch + imagenet
+ * models: cvtColor(BGR2RGB), cv2.resize(INTER_LINEAR) on uint8, /255, standardise, NCHW float32).
+ * A restatement of OpenCV's published fixed-point INTER_LINEAR for 8-bit, 3-channel images; parity
+ * with cv2 itself is not pinned in this repository, the kernel is pinned bit for bit to
+ * monocular_depth_estimation_trt_amd/preprocess.py:resize_linear_u8.  The contract:
+ *   per axis (dst outputs from src inputs)
+ *     scale = 1.0 / ((double)dst / (double)src)        float64; NOT src / dst
+ *     f     = (float)((d + 0.5) * scale - 0.5)         float64, rounded once to float32
+ *     s     = floor(f);  f -= s                        float32
+ *   horizontal axis only
+ *     s <  0         -> s = 0,         f = 0
+ *     s >= src_w - 1 -> s = src_w - 1, f = 0
+ *     second tap     = min(s + 1, src_w - 1)
+ *   vertical axis
+ *     f is not changed at the borders; both tap rows s and s + 1 are clamped to [0, src_h - 1]
+ *   coefficients, per axis (two separately rounded float32 products, half to even; they need not
+ *   sum to 2048)
+ *     c0 = rint((1.f - f) * 2048.f),  c1 = rint(f * 2048.f)
+ *   horizontal pass, exact integers
+ *     H = S[s] * a0 + S[s1] * a1
+ *   vertical pass
+ *     out = (((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) + 2) >> 2      (always 0..255)
+ *   special case: sw == 2 ow AND sh == 2 oh takes cv2's area path, out = (s00 + s01 + s10 + s11 + 2)
+ *     >> 2 over the 2x2 block (a 2x ratio on one axis only stays on the linear path).
+ * src is [batch][sh][pitch] bytes, 3 interleaved channels per pixel, pitch >= 3 * sw (ROI / aligned
+ * rows; bytes of a row past 3 * sw are never read); swap_rb != 0 writes source channel 2 - c to
+ * output channel c (BGR -> RGB; commutes with the resize, which is per channel).
+ * mde_op_resize_u8 writes uint8 NHWC [batch][oh][ow][3] (the "image_u8" binding of a uint8_nhwc
+ * engine); mde_op_resize_u8_norm writes float32 NCHW [batch][3][oh][ow] = lut3x256[c][value] (the
+ * "input" binding of a float engine), lut3x256 a device float[3][256] indexed by output channel and
+ * resized pixel value (preprocess.py:normalize_lut builds it in the reference's own dtypes).
+ * Both only enqueue one kernel on `stream` (no allocation, no synchronisation: capturable).
+ * MDE_ERR_ARG, before any device call: null pointer, non-positive size, pitch < 3 * sw. */
+int mde_op_resize_u8(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                     unsigned char* dst_u8, int oh, int ow, void* stream);
+int mde_op_resize_u8_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                          const float* lut3x256, float* dst_f32_nchw, int oh, int ow, void* stream);
 /* Depth Pro pyramid patches (upstream DepthProEncoder._create_pyramid + _split, reference engine input
  * "input"): fp32 NCHW image [batch][3][size][size] (size = 4 * 384) -> f16 patch-embed rows
  * [nseq * batch * 576][768] ((c, py, px) order), sequence s = patch * batch + image with the 25

@@ -1318,6 +1318,33 @@ int mde_op_depth_postprocess(const float* depth, int batch, int ih, int iw, floa
   OP_RET(launch_depth_postprocess(depth, batch, ih, iw, out, oh, ow, lo, hi, (hipStream_t)st), "depth_postprocess");
 }
 
+namespace {
+const char* resize_u8_arg_error(const void* src, const void* dst, int batch, int sh, int sw, int pitch, int oh,
+                                int ow) {
+  if (!src || !dst) return "null pointer";
+  if (batch < 1 || sh < 1 || sw < 1 || oh < 1 || ow < 1) return "batch and sizes must be positive";
+  if (pitch < 3 * (long long)sw) return "pitch < 3 * sw";
+  return nullptr;
+}
+}  // namespace
+
+int mde_op_resize_u8(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                     unsigned char* dst_u8, int oh, int ow, void* st) {
+  if (const char* why = resize_u8_arg_error(src, dst_u8, batch, sh, sw, pitch, oh, ow))
+    return fail(MDE_ERR_ARG, std::string("mde_op_resize_u8: ") + why);
+  OP_RET(launch_resize_u8(src, batch, sh, sw, pitch, swap_rb, nullptr, dst_u8, oh, ow, (hipStream_t)st),
+         "mde_op_resize_u8");
+}
+
+int mde_op_resize_u8_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                          const float* lut3x256, float* dst_f32_nchw, int oh, int ow, void* st) {
+  const char* why = resize_u8_arg_error(src, dst_f32_nchw, batch, sh, sw, pitch, oh, ow);
+  if (!why && !lut3x256) why = "null pointer";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_resize_u8_norm: ") + why);
+  OP_RET(launch_resize_u8(src, batch, sh, sw, pitch, swap_rb, lut3x256, dst_f32_nchw, oh, ow, (hipStream_t)st),
+         "mde_op_resize_u8_norm");
+}
+
 int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
   if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
   DpPyramid pyr;

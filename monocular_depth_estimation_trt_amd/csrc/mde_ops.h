@@ -199,6 +199,10 @@ hipError_t launch_patch_prep_u8(const unsigned char* img, h16* P, float* X, cons
                                 const float* cls_st = nullptr, float* P32 = nullptr);
 hipError_t launch_depth_postprocess(const float* in, int B, int ih, int iw, float* out, int oh, int ow, float lo,
                                     float hi, hipStream_t st);
+// preprocess.hip: cv2's uint8 INTER_LINEAR stretch of [B][sh][pitch] 3-channel rows; lut == nullptr:
+// dst uint8 NHWC [B][oh][ow][3]; else dst float NCHW [B][3][oh][ow] = lut[c][value] (lut float[3][256])
+hipError_t launch_resize_u8(const unsigned char* src, int B, int sh, int sw, int pitch, int swap_rb, const float* lut,
+                            void* dst, int oh, int ow, hipStream_t st);
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H,
                              int W, int ph, int pw, int T, int D, hipStream_t st, h16* Xh = nullptr,
                              float* lnst = nullptr, const float* cls_st = nullptr, float* P32 = nullptr);

@@ -10,8 +10,16 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
 
     python -m monocular_depth_estimation_trt_amd.models.depth_anything_v2.run \
         [--source synthetic:vits:metric | ckpt.pth] [--input x.npy] [--src-hw H W]
+        [--image photo.npy|photo.jpg] [--host-preprocess]
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
 
+`--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
+BGR array, or an image file if Pillow is installed -- taken through the
+reference's core/preprocess.py:preprocess_for (BGR->RGB, cv2 INTER_LINEAR
+stretch on uint8, /255, standardise) on the device, straight into the
+engine's input binding (preprocess.DevicePreprocess; `--host-preprocess`: the
+numpy version and the usual upload); `--src-hw` then defaults to the photo's
+own size.  The pre-process is outside the timed loop, as in the reference.
 `--input` is an already-preprocessed float32 NCHW [1,3,518,518] tensor (the
 reference's core/preprocess.py needs cv2, absent here), or for
 `--input-format uint8_nhwc` the uint8 [1,518,518,3] image the reference's
@@ -23,12 +31,16 @@ post-process runs on the device (postprocess.DevicePostprocess) unless
 
 import argparse
 import os
+import time
 
 import numpy as np
 
 from monocular_depth_estimation_trt_amd import bench, common, spec, weights
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
-from monocular_depth_estimation_trt_amd.common_runtime import allocate_buffers, do_inference, free_buffers
+from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
+                                                           resize_linear_u8)
+from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
+                                                               stream_synchronize)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -42,26 +54,74 @@ def postprocess(depth: np.ndarray, src_hw) -> np.ndarray:
     return torch.clamp(t, min=1e-3, max=1e3).numpy()
 
 
-def main(argv=None, model="depth_anything_v2"):
-    s = spec.load(model)
-    mc = spec.model_config_of(s)
+def build_parser(model="depth_anything_v2", mc=None):
+    mc = mc or spec.model_config_of(spec.load(model))
     input_h, input_w = mc["input_hw"]
     ap = argparse.ArgumentParser(prog=model)
     ap.add_argument("--source", default=f"synthetic:{mc['encoder']}:{mc['depth_type']}:1234")
     ap.add_argument("--engine", default=os.path.join(os.path.dirname(HERE), model, "engine",
                                                      f"{model}_{mc['encoder']}_{input_h}x{input_w}_fp16.mdeng"))
     ap.add_argument("--input", default="")
-    ap.add_argument("--src-hw", type=int, nargs=2, default=[2268, 3024])
+    ap.add_argument("--image", default="", help="source-resolution BGR photo: .npy (uint8 [H,W,3]) or an image file")
+    ap.add_argument("--host-preprocess", action="store_true",
+                    help="with --image: pre-process on the host (numpy) and upload, instead of on the device")
+    ap.add_argument("--src-hw", type=int, nargs=2, default=None,
+                    help="size of the returned map (default: the --image's own size, else 2268 3024)")
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out-dir", default=os.path.join(os.getcwd(), "reports", "bench"))
     ap.add_argument("--input-format", choices=("float32_nchw", "uint8_nhwc"), default="float32_nchw")
     ap.add_argument("--host-postprocess", action="store_true")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def _device_preprocess(img, model, input_hw, input_format, mem, stream):
+    """DevicePreprocess into the engine's input binding `mem.device`, timed with
+    hipEvents (H2D of the frame + the kernel); the pinned side of the binding
+    gets the same bytes back, so the timed loop's upload is a no-op in value."""
+    import ctypes as C
+    ev = [C.c_void_p(), C.c_void_p()]
+    for e in ev:
+        hip_call("mde_rt_event_create", C.byref(e))
+    try:
+        with DevicePreprocess(img.shape[0], img.shape[1], *input_hw, model, output=input_format) as pre:
+            hip_call("mde_rt_event_record", ev[0], C.c_void_p(stream))
+            pre.run(img, mem.device, stream)
+            hip_call("mde_rt_event_record", ev[1], C.c_void_p(stream))
+            hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
+                     mem.nbytes, C.c_void_p(stream))
+            stream_synchronize(stream)
+        ms = C.c_float()
+        hip_call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
+    finally:
+        for e in ev:
+            hip_call("mde_rt_event_destroy", e)
+    return float(ms.value)
+
+
+def main(argv=None, model="depth_anything_v2"):
+    mc = spec.model_config_of(spec.load(model))
+    input_h, input_w = mc["input_hw"]
+    a = build_parser(model, mc).parse_args(argv)
     u8 = a.input_format == "uint8_nhwc"
+    if a.image and a.input:
+        raise SystemExit("--image and --input are exclusive")
+    if a.host_preprocess and not a.image:
+        raise SystemExit("--host-preprocess needs --image")
+    img = load_image_bgr(a.image) if a.image else None
+    if a.src_hw is None:
+        a.src_hw = list(img.shape[:2]) if img is not None else [2268, 3024]
     if u8 and a.engine.endswith("_fp16.mdeng"):
         a.engine = a.engine[:-len("_fp16.mdeng")] + "_u8_fp16.mdeng"
-    if u8:
+    if img is not None and a.host_preprocess:
+        t0 = time.perf_counter()
+        x = (resize_linear_u8(img[:, :, ::-1], input_h, input_w)[None] if u8
+             else preprocess_host(img, model, (input_h, input_w))[0])
+        print(f"[MDET] preprocess (host, numpy) {img.shape[0]}x{img.shape[1]} -> {input_h}x{input_w} : "
+              f"{(time.perf_counter() - t0) * 1e3:0.3f} ms")
+    elif img is not None:
+        x = None  # filled on the device, below
+    elif u8:
         x = (np.load(a.input, allow_pickle=False).astype(np.uint8) if a.input
              else weights.synthetic_images_u8(1, input_h, input_w, first_seed=0))
     else:
@@ -73,7 +133,14 @@ def main(argv=None, model="depth_anything_v2"):
                            input_format=a.input_format) as engine, \
             engine.create_execution_context() as context:
         inputs, outputs, bindings, stream = allocate_buffers(engine, output_shape, profile_idx=0)
-        inputs[0].host = x
+        if x is None:
+            ms = _device_preprocess(img, model, (input_h, input_w), a.input_format, inputs[0], stream)
+            print(f"[MDET] preprocess (device, H2D + kernel, hipEvents) {img.shape[0]}x{img.shape[1]} -> "
+                  f"{input_h}x{input_w} {a.input_format} : {ms:0.3f} ms")
+            x = inputs[0].host[:3 * input_h * input_w].reshape(
+                (1, input_h, input_w, 3) if u8 else (1, 3, input_h, input_w)).copy()
+        else:
+            inputs[0].host = x
         outs, samples = bench.measure(
             lambda: do_inference(context, engine=engine, bindings=bindings, inputs=inputs, outputs=outputs,
                                  stream=stream), warmup=a.warmup, iterations=a.iterations)

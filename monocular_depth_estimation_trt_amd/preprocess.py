@@ -1,0 +1,233 @@
+"""Pre-process for the DA-V2 family (the input half): the
+reference's `core/preprocess.py:preprocess_for` for `depth_anything_v2`,
+`depth_anything_ac` and `distill_any_depth` -- cvtColor(BGR2RGB), a
+`cv2.resize(INTER_LINEAR)` stretch on uint8 to the engine size, /255, ImageNet
+standardise, NCHW float32 -- on the host in numpy (`preprocess_host`) and on
+the device as one HIP kernel (`DevicePreprocess`, csrc/preprocess.hip).
+
+`cv2` is not a dependency.  `resize_linear_u8` restates OpenCV's published
+fixed-point algorithm for 8-bit images (the contract is spelled out in
+include/mde.h at mde_op_resize_u8); parity with cv2 itself is not pinned here
+("Device preprocess").  What is pinned: the kernel is bit-identical
+to `resize_linear_u8`, and `resize_linear_u8` stays within one level of exact
+bilinear interpolation.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _lib
+from .common_runtime import HostDeviceMem, stream_synchronize
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+# model -> dtype of the /255 division (core/preprocess.py:_builders scale_dtype); the
+# standardise step is float64 for all three
+SCALE_DTYPE = {"depth_anything_v2": np.float64, "distill_any_depth": np.float64, "depth_anything_ac": np.float32}
+OUTPUTS = ("float32_nchw", "uint8_nhwc")
+COEF_BITS = 11  # cv2's INTER_RESIZE_COEF_BITS: weights are multiples of 1 / 2048
+
+
+def _axis_table(dst: int, src: int, clamp_fraction: bool):
+    """Per output index of one axis: (tap0, tap1, w0, w1) as integer arrays."""
+    scale = 1.0 / (float(dst) / float(src))  # float64; not src / dst
+    pos = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    base = np.floor(pos)
+    frac = pos - base  # float32
+    lo = base.astype(np.int32)
+    if clamp_fraction:  # horizontal: the border pixels are copied, not blended
+        frac = np.where((lo < 0) | (lo >= src - 1), np.float32(0), frac)
+    one, full = np.float32(1), np.float32(1 << COEF_BITS)
+    w0 = np.rint((one - frac) * full).astype(np.int32)
+    w1 = np.rint(frac * full).astype(np.int32)
+    return np.clip(lo, 0, src - 1), np.clip(lo + 1, 0, src - 1), w0, w1
+
+
+def resize_linear_u8(img_hwc_u8: np.ndarray, oh: int, ow: int) -> np.ndarray:
+    """`cv2.resize(img, (ow, oh), interpolation=cv2.INTER_LINEAR)` for a uint8
+    [H, W, C] image, in numpy integer arithmetic: whole-image gathers through
+    per-axis tables, the horizontal pass first (exact integers), then the
+    vertical pass with cv2's two truncating shifts.  An exact 2x reduction on
+    both axes is cv2's area path (the rounded mean of each 2x2 block)."""
+    img = np.asarray(img_hwc_u8)
+    if img.dtype != np.uint8 or img.ndim != 3:
+        raise ValueError(f"resize_linear_u8 wants a uint8 [H, W, C] image, got {img.dtype} {img.shape}")
+    sh, sw = img.shape[:2]
+    oh, ow = int(oh), int(ow)
+    if oh < 1 or ow < 1 or sh < 1 or sw < 1:
+        raise ValueError("resize_linear_u8: sizes must be positive")
+    if sw == 2 * ow and sh == 2 * oh:
+        blocks = img.astype(np.int32).reshape(oh, 2, ow, 2, -1)
+        return ((blocks.sum(axis=(1, 3)) + 2) >> 2).astype(np.uint8)
+    x0, x1, a0, a1 = _axis_table(ow, sw, clamp_fraction=True)
+    y0, y1, b0, b1 = _axis_table(oh, sh, clamp_fraction=False)
+    # int32 holds every intermediate: H <= 255 * 2049, b * (H >> 4) <= 2048 * 32656
+    rows = img[:, x0].astype(np.int32) * a0[None, :, None] + img[:, x1].astype(np.int32) * a1[None, :, None]
+    rows >>= 4
+    top = (rows[y0] * b0[:, None, None]) >> 16
+    bottom = (rows[y1] * b1[:, None, None]) >> 16
+    out = (top + bottom + 2) >> 2
+    return out.astype(np.uint8)
+
+
+def normalize_lut(model: str) -> np.ndarray:
+    """float32 [3][256]: channel c of pixel value u after the reference's
+    `scale` and `standardize` for `model`, computed in their dtypes."""
+    if model not in SCALE_DTYPE:
+        raise KeyError(f"no preprocessing declared for {model!r} (have {sorted(SCALE_DTYPE)})")
+    u = np.arange(256, dtype=np.uint8)[:, None].repeat(3, axis=1)  # [256][3]: every value in every channel
+    return np.ascontiguousarray(_normalize(u, model).T)
+
+
+def _normalize(img_u8: np.ndarray, model: str) -> np.ndarray:
+    """[..., 3] uint8 RGB -> float32, the reference's scale() then standardize()."""
+    x = img_u8.astype(SCALE_DTYPE[model]) / 255.0  # float32 stays float32 against a Python float
+    x = (x - np.asarray(IMAGENET_MEAN, np.float64)) / np.asarray(IMAGENET_STD, np.float64)  # float64
+    return x.astype(np.float32)
+
+
+def check_second_stage(model: str, h: int, w: int) -> None:
+    """The reference runs a second, cubic resize on the float image
+    (keep-ratio for v2 / ac, snap for distill); at its built profiles that is
+    the identity, and only then is this module its counterpart."""
+    if model not in SCALE_DTYPE:
+        raise KeyError(f"no preprocessing declared for {model!r} (have {sorted(SCALE_DTYPE)})")
+    if h % 14 or w % 14 or (model != "distill_any_depth" and h > w):
+        raise ValueError(f"{model} at {h}x{w}: the reference's second resize stage is not the identity there "
+                         f"(needs multiples of 14{'' if model == 'distill_any_depth' else ' and h <= w'})")
+
+
+def preprocess_host(img_bgr: np.ndarray, model: str, size: Tuple[int, int]):
+    """BGR uint8 [H, W, 3] frame -> (float32 [1, 3, h, w] blob, (src_h, src_w)):
+    `core/preprocess.py:preprocess_for(img_bgr, model, size)` on the host."""
+    h, w = int(size[0]), int(size[1])
+    check_second_stage(model, h, w)
+    img = np.asarray(img_bgr)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"preprocess_host wants a uint8 [H, W, 3] BGR image, got {img.dtype} {img.shape}")
+    rgb = resize_linear_u8(img[:, :, ::-1], h, w)
+    blob = np.ascontiguousarray(_normalize(rgb, model).transpose(2, 0, 1)[None])
+    return blob, (img.shape[0], img.shape[1])
+
+
+def load_image_bgr(path: str) -> np.ndarray:
+    """uint8 [H, W, 3] BGR: a .npy holding exactly that, or any image file
+    Pillow can decode (its decoders are not guaranteed byte-identical to
+    cv2.imread's)."""
+    if path.lower().endswith(".npy"):
+        img = np.load(path, allow_pickle=False)
+    else:
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise RuntimeError(f"decoding {path} needs Pillow, which is not installed; convert the image to a "
+                               f".npy holding a uint8 [H, W, 3] BGR array instead") from e
+        with Image.open(path) as im:
+            img = np.asarray(im.convert("RGB"))[:, :, ::-1]
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"{path}: expected a uint8 [H, W, 3] BGR image, got {img.dtype} {img.shape}")
+    return np.ascontiguousarray(img)
+
+
+def resize_u8(d_src: int, batch: int, sh: int, sw: int, pitch: int, swap_rb: bool, d_dst: int, oh: int, ow: int,
+              stream: int = 0, d_lut: int = 0) -> None:
+    """Device pointers in/out, enqueued on `stream`: uint8 NHWC out, or with
+    `d_lut` (device float[3][256]) float32 NCHW out."""
+    head = (C.c_void_p(int(d_src)), int(batch), int(sh), int(sw), int(pitch), int(bool(swap_rb)))
+    tail = (C.c_void_p(int(d_dst)), int(oh), int(ow), C.c_void_p(int(stream or 0)))
+    if d_lut:
+        _lib.call("mde_op_resize_u8_norm", *head, C.c_void_p(int(d_lut)), *tail)
+    else:
+        _lib.call("mde_op_resize_u8", *head, *tail)
+
+
+class DevicePreprocess:
+    """Owns the source frame (pinned host + device) and the device LUT;
+    `run(img_bgr, d_dst, stream)` copies the frame to the device and enqueues
+    the resize straight into the engine's input binding `d_dst`:
+    output "float32_nchw" -> [batch][3][oh][ow] float32 (binding "input"),
+    "uint8_nhwc" -> [batch][oh][ow][3] uint8 RGB (binding "image_u8").
+    run() and run_device() only enqueue.  run() stages the frame in the one
+    pinned buffer this object owns and copies it from there asynchronously, so
+    the caller must synchronize `stream` (or otherwise know that copy has
+    finished) before the next run() overwrites the buffer; fill_binding() does.
+    The result is on the device in stream order: anything that reads `d_dst`
+    must be enqueued on `stream` or after a synchronize of it (the streams of
+    allocate_buffers are non-blocking: the null stream does not wait for them)."""
+
+    def __init__(self, src_h: int, src_w: int, oh: int, ow: int, model: str, output: str = "float32_nchw",
+                 batch: int = 1):
+        if output not in OUTPUTS:
+            raise ValueError(f"output must be one of {OUTPUTS}, got {output!r}")
+        check_second_stage(model, int(oh), int(ow))
+        self.src = (int(src_h), int(src_w))
+        self.dst = (int(oh), int(ow))
+        self.batch = int(batch)
+        self.output = output
+        self.mem: Optional[HostDeviceMem] = HostDeviceMem(self.batch * self.src[0] * self.src[1] * 3, np.uint8)
+        self.lut: Optional[HostDeviceMem] = None
+        if output == "float32_nchw":
+            try:
+                self.lut = HostDeviceMem(3 * 256, np.float32)
+                self.lut.host = normalize_lut(model)
+                _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(self.lut.device),
+                          self.lut.host.ctypes.data_as(C.c_void_p), self.lut.nbytes, None)
+                _lib.call("mde_rt_device_synchronize")
+            except Exception:
+                self.free()
+                raise
+
+    def run_device(self, d_src: int, pitch: int, d_dst: int, stream: int, swap_rb: bool = True) -> None:
+        """Frames already on the device: [batch][src_h][pitch] bytes, BGR unless swap_rb=False."""
+        if self.mem is None:
+            raise RuntimeError("DevicePreprocess already freed")
+        resize_u8(d_src, self.batch, self.src[0], self.src[1], pitch, swap_rb, d_dst, self.dst[0], self.dst[1],
+                  stream, self.lut.device if self.lut is not None else 0)
+
+    def run(self, img_bgr: np.ndarray, d_dst: int, stream: int) -> None:
+        if self.mem is None:
+            raise RuntimeError("DevicePreprocess already freed")
+        img = np.asarray(img_bgr)
+        want = (self.batch, self.src[0], self.src[1], 3)
+        if img.dtype != np.uint8 or img.shape not in (want, want[1:] if self.batch == 1 else want):
+            raise ValueError(f"DevicePreprocess.run wants a uint8 BGR array of shape {want}, got {img.dtype} "
+                             f"{img.shape}")
+        host = self.mem.host
+        np.copyto(host.reshape(want), img.reshape(want))
+        _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(self.mem.device), host.ctypes.data_as(C.c_void_p),
+                  host.nbytes, C.c_void_p(int(stream or 0)))
+        self.run_device(self.mem.device, 3 * self.src[1], d_dst, stream)
+
+    def fill_binding(self, img_bgr: np.ndarray, binding: HostDeviceMem, stream: int) -> None:
+        """run() into an input binding of allocate_buffers, then bring the same
+        bytes back into its pinned host side in stream order and synchronize:
+        do_inference's own upload of `binding.host` then rewrites the device
+        side with what is already there."""
+        need = self.batch * self.dst[0] * self.dst[1] * 3 * (4 if self.lut is not None else 1)
+        if binding.nbytes < need:
+            raise ValueError(f"binding holds {binding.nbytes} bytes, the {self.output} result needs {need}")
+        self.run(img_bgr, binding.device, stream)
+        _lib.call("mde_rt_memcpy_dtoh_async", binding.host.ctypes.data_as(C.c_void_p), C.c_void_p(binding.device),
+                  need, C.c_void_p(int(stream or 0)))
+        stream_synchronize(stream)
+
+    def free(self) -> None:
+        for m in (self.mem, self.lut):
+            if m is not None:
+                m.free()
+        self.mem = self.lut = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+__all__ = ["resize_linear_u8", "normalize_lut", "preprocess_host", "load_image_bgr", "resize_u8",
+           "DevicePreprocess", "check_second_stage"]
