@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MDE_ABI_VERSION 9
+#define MDE_ABI_VERSION 10
 
 typedef enum {
   MDE_OK = 0,
@@ -325,6 +325,42 @@ int mde_op_resize_u8(const unsigned char* src, int batch, int sh, int sw, int pi
                      unsigned char* dst_u8, int oh, int ow, void* stream);
 int mde_op_resize_u8_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
                           const float* lut3x256, float* dst_f32_nchw, int oh, int ow, void* stream);
+/* Depth Pro photo path (since ABI 10): the two ends of reference models/depth_pro/onnx2trt.py around
+ * the engine.  mde_op_dp_preprocess restates :56-74, ToTensor + Normalize(0.5, 0.5) +
+ * F.interpolate(bilinear, align_corners=False): src is a uint8 photo [batch][sh][pitch], 3 interleaved
+ * channels per pixel, with the rules of mde_op_resize_u8 (pitch >= 3 * sw, bytes of a row past 3 * sw
+ * are never read, swap_rb != 0 writes source channel 2 - c to output channel c); dst is float32 NCHW
+ * [batch][3][oh][ow], the engine's "input" binding.  The contract:
+ *   value of a pixel byte u:  lut[u], a device float[256] the caller passes
+ *                             (host builds it as ((float32(u) / 255f) - 0.5f) / 0.5f, all float32)
+ *   per axis (dst outputs from src inputs), every operation rounded to float32 separately, never fused:
+ *     scale = (float)src / (float)dst
+ *     x  = scale * ((float)d + 0.5f) - 0.5f;   x = max(x, 0)
+ *     i0 = min((int)x, src - 1);  i1 = min(i0 + 1, src - 1)
+ *     l1 = clamp(x - (float)i0, 0, 1);  l0 = 1 - l1
+ *   out = b0 * (a0 * v00 + a1 * v01) + b1 * (a0 * v10 + a1 * v11)     (a: horizontal, b: vertical)
+ * mde_op_dp_postprocess restates :118-134: inv is "canonical_inverse_depth", fp32 [batch][ih][iw];
+ * depth is metric depth, fp32 [batch][oh][ow].  fov_deg is a device float[batch] (the engine's second
+ * output binding) and may be null; f_px is a host float, used for every image when fov_deg is null (the
+ * reference's f_px0 / EXIF path) and then > 0; f_px_out is a device float[batch], may be null, and
+ * receives the focal length actually used.  The contract:
+ *   f  = fov_deg ? (0.5f * ow) / tanf(0.5f * (fov_deg[b] * (pi/180))) : f_px
+ *   k  = (float)ow / f
+ *   tap value = inv * k                 (rounded, before blending - the reference scales, then resizes)
+ *   m  = the same bilinear as above, [ih][iw] -> [oh][ow]
+ *   depth = 1.0f / min(max(m, 1e-4f), 1e4f)        (IEEE division; the build has no fast-math, keep it so)
+ *   a NaN m stays NaN, as in torch.clamp: a non-finite engine output is not turned into a finite depth
+ * The kernels are pinned bit for bit to monocular_depth_estimation_trt_amd/preprocess.py:
+ * resize_bilinear_f32 and postprocess.py:depth_pro_postprocess_np (except tanf, the device's own), and
+ * those to torch on the CPU within a derived tolerance ("Depth Pro photo path").
+ * Both only enqueue one kernel on `stream` (no allocation, no synchronisation: capturable).
+ * MDE_ERR_ARG, before any device call: a null required pointer, a non-positive size, pitch < 3 * sw,
+ * a source or destination plane of 2^31 - 256 elements or more, batch > 65535, post-process with null
+ * fov_deg and f_px <= 0. */
+int mde_op_dp_preprocess(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                         const float* lut256, float* dst_f32_nchw, int oh, int ow, void* stream);
+int mde_op_dp_postprocess(const float* inv, int batch, int ih, int iw, const float* fov_deg, float f_px,
+                          float* f_px_out, float* depth, int oh, int ow, void* stream);
 /* Depth Pro pyramid patches (upstream DepthProEncoder._create_pyramid + _split, reference engine input
  * "input"): fp32 NCHW image [batch][3][size][size] (size = 4 * 384) -> f16 patch-embed rows
  * [nseq * batch * 576][768] ((c, py, px) order), sequence s = patch * batch + image with the 25

@@ -152,6 +152,10 @@ PROTOTYPES = {
     "mde_op_resize_u8": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p],
     "mde_op_resize_u8_norm": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                               c_void_p],
+    "mde_op_dp_preprocess": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                             c_void_p],
+    "mde_op_dp_postprocess": [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int,
+                              c_void_p],
     "mde_op_qk_norm_rope": [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_void_p, c_float, c_float, c_void_p],
     "mde_op_tap_concat_ln": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
                              c_void_p],

@@ -1345,6 +1345,36 @@ int mde_op_resize_u8_norm(const unsigned char* src, int batch, int sh, int sw, i
          "mde_op_resize_u8_norm");
 }
 
+namespace {
+// the Depth Pro photo ops index a plane with an int and put the batch on grid.y
+const char* dp_photo_geometry_error(int batch, int sh, int sw, int oh, int ow) {
+  if (batch < 1 || sh < 1 || sw < 1 || oh < 1 || ow < 1) return "batch and sizes must be positive";
+  const long long lim = 0x7fffffffLL - 256;
+  if ((long long)sh * sw >= lim || (long long)oh * ow >= lim) return "a plane of 2^31 - 256 elements or more";
+  if (batch > 65535) return "batch > 65535";
+  return nullptr;
+}
+}  // namespace
+
+int mde_op_dp_preprocess(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                         const float* lut256, float* dst_f32_nchw, int oh, int ow, void* st) {
+  const char* why = dp_photo_geometry_error(batch, sh, sw, oh, ow);
+  if (!src || !lut256 || !dst_f32_nchw) why = "null pointer";
+  if (!why && pitch < 3 * (long long)sw) why = "pitch < 3 * sw";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_dp_preprocess: ") + why);
+  OP_RET(launch_dp_preprocess(src, batch, sh, sw, pitch, swap_rb, lut256, dst_f32_nchw, oh, ow, (hipStream_t)st),
+         "mde_op_dp_preprocess");
+}
+
+int mde_op_dp_postprocess(const float* inv, int batch, int ih, int iw, const float* fov_deg, float f_px,
+                          float* f_px_out, float* depth, int oh, int ow, void* st) {
+  const char* why = (!inv || !depth) ? "null pointer" : dp_photo_geometry_error(batch, ih, iw, oh, ow);
+  if (!why && !fov_deg && !(f_px > 0.f)) why = "fov_deg is null and f_px <= 0";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_dp_postprocess: ") + why);
+  OP_RET(launch_dp_postprocess(inv, batch, ih, iw, fov_deg, f_px, f_px_out, depth, oh, ow, (hipStream_t)st),
+         "mde_op_dp_postprocess");
+}
+
 int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
   if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
   DpPyramid pyr;

@@ -203,6 +203,15 @@ hipError_t launch_depth_postprocess(const float* in, int B, int ih, int iw, floa
 // dst uint8 NHWC [B][oh][ow][3]; else dst float NCHW [B][3][oh][ow] = lut[c][value] (lut float[3][256])
 hipError_t launch_resize_u8(const unsigned char* src, int B, int sh, int sw, int pitch, int swap_rb, const float* lut,
                             void* dst, int oh, int ow, hipStream_t st);
+// depth_pro_photo.hip: Depth Pro's pre-process (uint8 [B][sh][pitch] photo -> lut[u], torch bilinear
+// align_corners=False -> float NCHW [B][3][oh][ow]; lut float[256]) and post-process (inverse depth
+// [B][ih][iw] * ow / f, the same bilinear to [B][oh][ow], 1 / clamp(., 1e-4, 1e4); f from fov_deg [B]
+// when non-null, else f_px; f_px_out [B] optional).  No argument checks here: the ABI wrappers in
+// engine.hip hold the only copy of the limits
+hipError_t launch_dp_preprocess(const unsigned char* src, int B, int sh, int sw, int pitch, int swap_rb,
+                                const float* lut, float* dst, int oh, int ow, hipStream_t st);
+hipError_t launch_dp_postprocess(const float* inv, int B, int ih, int iw, const float* fov_deg, float f_px,
+                                 float* f_px_out, float* out, int oh, int ow, hipStream_t st);
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H,
                              int W, int ph, int pw, int T, int D, hipStream_t st, h16* Xh = nullptr,
                              float* lnst = nullptr, const float* cls_st = nullptr, float* P32 = nullptr);

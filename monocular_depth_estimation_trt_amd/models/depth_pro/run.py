@@ -1,7 +1,7 @@
 """Depth Pro on MI355X -- the counterpart of the reference driver
 `models/depth_pro/onnx2trt.py:main` (:42-125), same sequence:
 
-  input (normalised to [-1, 1], host-resized to 1536^2 with torch bilinear,
+  photo (normalised to [-1, 1], resized to 1536^2 with torch bilinear,
   align_corners=False) -> get_engine -> create_execution_context ->
   allocate_buffers -> bench.measure(do_inference) (20 warmup / 100
   iterations) -> post-process outside the timed loop (focal length from the
@@ -9,21 +9,38 @@
   depth = 1 / clamp(inv, 1e-4, 1e4)) -> bench.record
 
     python -m monocular_depth_estimation_trt_amd.models.depth_pro.run \
-        [--source synthetic:depth_pro | DepthPro.safetensors] [--input x.npy] [--src-hw H W]
+        [--source synthetic:depth_pro | DepthPro.safetensors] [--image photo.npy|photo.jpg]
+        [--input x.npy] [--src-hw H W] [--f-px F] [--host-preprocess] [--host-postprocess]
 
-`--input` is a float32 NCHW [1,3,H,W] image already normalised to [-1, 1]
-(the reference's cv2 read is unavailable here); it is resized to 1536^2 on the
-host like the reference does.  Without it a synthetic 1536^2 image is used.
+`--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
+BGR array, or an image file if Pillow is installed.  It is normalised and
+resized on the device straight into the engine's input binding
+(preprocess.DepthProPreprocess; `--host-preprocess`: the numpy statement of the
+same arithmetic and the usual upload), and `--src-hw` defaults to its size.
+`--input` is a float32 NCHW [1,3,H,W] image already normalised to [-1, 1]; it
+is resized to 1536^2 on the host with torch like the reference does.  Without
+either a synthetic 1536^2 image is used.
+
+The post-process reads the engine's output bindings in place on the driver's
+stream (postprocess.DepthProDevicePostprocess) and downloads the metric depth
+at the source size; `--host-postprocess` downloads the 1536^2 map and runs the
+reference's torch-CPU version.  `--f-px` is the reference's f_px0: a known
+focal length in pixels instead of the predicted one.
 """
 
 import argparse
+import ctypes as C
 import os
+import time
 
 import numpy as np
 
 from monocular_depth_estimation_trt_amd import bench, common, spec, weights_depth_pro
-from monocular_depth_estimation_trt_amd.common_runtime import allocate_buffers, do_inference, free_buffers
-from monocular_depth_estimation_trt_amd.postprocess import depth_pro_postprocess
+from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
+                                                               stream_synchronize)
+from monocular_depth_estimation_trt_amd.postprocess import DepthProDevicePostprocess, depth_pro_postprocess
+from monocular_depth_estimation_trt_amd.preprocess import (DepthProPreprocess, load_image_bgr,
+                                                           preprocess_depth_pro_host)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -39,41 +56,146 @@ def preprocess(x: np.ndarray, size: int) -> np.ndarray:
     return F.interpolate(t, size=(size, size), mode="bilinear", align_corners=False).numpy()
 
 
-def main(argv=None, model="depth_pro"):
-    s = spec.load(model)
-    size = spec.size_of(s)[0]
+def build_parser(model="depth_pro", size=None):
+    size = size or spec.size_of(spec.load(model))[0]
     ap = argparse.ArgumentParser(prog=model)
     ap.add_argument("--source", default="synthetic:depth_pro:dinov2l16_384:4321")
     ap.add_argument("--engine", default=os.path.join(HERE, "engine", f"depth_pro_{size}x{size}_fp16.mdeng"))
     ap.add_argument("--input", default="")
+    ap.add_argument("--image", default="", help="source-resolution BGR photo: .npy (uint8 [H,W,3]) or an image file")
+    ap.add_argument("--host-preprocess", action="store_true",
+                    help="with --image: pre-process on the host (numpy) and upload, instead of on the device")
+    ap.add_argument("--host-postprocess", action="store_true",
+                    help="download the engine's map and post-process with torch on the CPU")
+    ap.add_argument("--f-px", type=float, default=None,
+                    help="focal length in pixels (the reference's f_px0) instead of the predicted one")
     ap.add_argument("--src-hw", type=int, nargs=2, default=None,
-                    help="source image size for the post-process (default: the input's own size)")
+                    help="source image size for the post-process (default: the image's / input's own size)")
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out-dir", default=os.path.join(os.getcwd(), "reports", "bench"))
-    a = ap.parse_args(argv)
-    x = (np.load(a.input, allow_pickle=False).astype(np.float32) if a.input
-         else weights_depth_pro.synthetic_images(1, size, first_seed=0))
-    H, W = x.shape[-2:]
+    return ap
+
+
+class _Events:
+    """A hipEvent pair on one stream; ms() after the stream has synchronized."""
+
+    def __init__(self, stream):
+        self.stream = C.c_void_p(stream)
+        self.ev = [C.c_void_p(), C.c_void_p()]
+        for e in self.ev:
+            hip_call("mde_rt_event_create", C.byref(e))
+
+    def mark(self, i):
+        hip_call("mde_rt_event_record", self.ev[i], self.stream)
+
+    def ms(self):
+        ms = C.c_float()
+        hip_call("mde_rt_event_elapsed_ms", C.byref(ms), self.ev[0], self.ev[1])
+        return float(ms.value)
+
+    def free(self):
+        for e in self.ev:
+            hip_call("mde_rt_event_destroy", e)
+
+
+def _device_preprocess(img, size, mem, stream):
+    """DepthProPreprocess into the engine's input binding `mem.device`, timed
+    with hipEvents (H2D of the frame + the kernel); the pinned side of the
+    binding gets the same bytes back, so the timed loop's upload is a no-op in
+    value."""
+    ev = _Events(stream)
+    try:
+        with DepthProPreprocess(img.shape[0], img.shape[1], size) as pre:
+            ev.mark(0)
+            pre.run(img, mem.device, stream)
+            ev.mark(1)
+            hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
+                     mem.nbytes, C.c_void_p(stream))
+            stream_synchronize(stream)
+        return ev.ms()
+    finally:
+        ev.free()
+
+
+def _device_postprocess(outputs, size, src_hw, f_px, stream):
+    """DepthProDevicePostprocess on the output bindings in place, timed with
+    hipEvents (kernel + D2H of the depth map and the focal length)."""
+    if f_px is None and len(outputs) < 2:
+        raise SystemExit("this engine has no fov_deg output: pass --f-px")
+    ev = _Events(stream)
+    try:
+        with DepthProDevicePostprocess(1, size, size, *src_hw) as pp:
+            ev.mark(0)
+            pp.enqueue(outputs[0].device, outputs[1].device if len(outputs) > 1 else 0, stream, f_px=f_px)
+            ev.mark(1)
+            stream_synchronize(stream)
+            depth, f = pp.result()
+            return depth[0].copy(), float(f[0]), ev.ms()
+    finally:
+        ev.free()
+
+
+def main(argv=None, model="depth_pro"):
+    s = spec.load(model)
+    size = spec.size_of(s)[0]
+    a = build_parser(model, size).parse_args(argv)
+    if a.image and a.input:
+        raise SystemExit("--image and --input are exclusive")
+    if a.host_preprocess and not a.image:
+        raise SystemExit("--host-preprocess needs --image")
+    if a.f_px is not None and not a.f_px > 0:
+        raise SystemExit("--f-px must be positive")
+    img = load_image_bgr(a.image) if a.image else None
+    if img is not None and not a.host_preprocess:
+        x = None  # filled on the device, below
+        H, W = img.shape[:2]
+    else:
+        t0 = time.perf_counter()
+        if img is not None:
+            x, (H, W) = preprocess_depth_pro_host(img, size)
+            how = "host, numpy"
+        else:
+            x = (np.load(a.input, allow_pickle=False).astype(np.float32) if a.input
+                 else weights_depth_pro.synthetic_images(1, size, first_seed=0))
+            H, W = x.shape[-2:]
+            x = preprocess(x, size)
+            how = "host, torch resize of a normalised tensor"
+        print(f"[MDET] preprocess ({how}) {H}x{W} -> {size}x{size} : {(time.perf_counter() - t0) * 1e3:0.3f} ms")
     src_hw = tuple(a.src_hw) if a.src_hw else (H, W)
-    x = preprocess(x, size)
     output_shapes = (1, 1, size, size)
     with common.get_engine(a.source, a.engine, "fp16", None, input_hw=(size, size)) as engine, \
             engine.create_execution_context() as context:
         inputs, outputs, bindings, stream = allocate_buffers(engine)
-        inputs[0].host = x
+        if x is None:
+            ms = _device_preprocess(img, size, inputs[0], stream)
+            print(f"[MDET] preprocess (device, H2D + kernel, hipEvents) {H}x{W} -> {size}x{size} : {ms:0.3f} ms")
+            x = inputs[0].host[:3 * size * size].reshape(1, 3, size, size).copy()
+        else:
+            inputs[0].host = x
         outs, samples = bench.measure(
             lambda: do_inference(context, engine=engine, bindings=bindings, inputs=inputs, outputs=outputs,
                                  stream=stream), warmup=a.warmup, iterations=a.iterations)
-        inv = outs[0].reshape(output_shapes).copy()
-        fov = outs[1].copy() if len(outs) > 1 else None
-        depth, f_px = depth_pro_postprocess(inv, fov, src_hw)
+        if a.host_postprocess:
+            t0 = time.perf_counter()
+            inv = outs[0].reshape(output_shapes).copy()
+            fov = outs[1].copy() if len(outs) > 1 else None
+            depth, f_px = depth_pro_postprocess(inv, fov, src_hw, f_px=a.f_px)
+            print(f"[MDET] postprocess (host, torch) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
+                  f"{(time.perf_counter() - t0) * 1e3:0.3f} ms")
+        else:  # the engine's outputs are still in outputs[*].device
+            depth, f_px, ms = _device_postprocess(outputs, size, src_hw, a.f_px, stream)
+            print(f"[MDET] postprocess (device, kernel + D2H, hipEvents) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
+                  f"{ms:0.3f} ms")
         bench.record(model, samples, encoder="fixed", warmup=a.warmup, precision="fp16", profile="native",
                      input_h=size, input_w=size, engine_path=a.engine, outputs={"depth": depth, "f_px": np.array(f_px)},
                      notes=f"source={a.source}; 1536x1536 is upstream fixed", model_input=x, out_dir=a.out_dir)
         free_buffers(inputs, outputs, stream)
     print(f"[MDET] max : {depth.max()} , min : {depth.min()}")
-    print(f"[MDET] predicted Focal length (by Depth Pro) : {f_px:0.2f}")
+    if a.f_px is not None:
+        print(f"[MDET] focal length (given) : {f_px:0.2f}")
+    else:
+        print(f"[MDET] predicted Focal length (by Depth Pro) : {f_px:0.2f}")
     return depth, f_px
 
 

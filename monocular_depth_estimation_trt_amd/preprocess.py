@@ -11,6 +11,9 @@ include/mde.h at mde_op_resize_u8); parity with cv2 itself is not pinned here
 ("Device preprocess").  What is pinned: the kernel is bit-identical
 to `resize_linear_u8`, and `resize_linear_u8` stays within one level of exact
 bilinear interpolation.
+
+Depth Pro's pre-process is another function (normalise, then torch's float32
+bilinear) and has its own section at the end of this module.
 """
 
 from __future__ import annotations
@@ -145,56 +148,48 @@ def resize_u8(d_src: int, batch: int, sh: int, sw: int, pitch: int, swap_rb: boo
         _lib.call("mde_op_resize_u8", *head, *tail)
 
 
-class DevicePreprocess:
-    """Owns the source frame (pinned host + device) and the device LUT;
-    `run(img_bgr, d_dst, stream)` copies the frame to the device and enqueues
-    the resize straight into the engine's input binding `d_dst`:
-    output "float32_nchw" -> [batch][3][oh][ow] float32 (binding "input"),
-    "uint8_nhwc" -> [batch][oh][ow][3] uint8 RGB (binding "image_u8").
-    run() and run_device() only enqueue.  run() stages the frame in the one
-    pinned buffer this object owns and copies it from there asynchronously, so
-    the caller must synchronize `stream` (or otherwise know that copy has
-    finished) before the next run() overwrites the buffer; fill_binding() does.
-    The result is on the device in stream order: anything that reads `d_dst`
-    must be enqueued on `stream` or after a synchronize of it (the streams of
-    allocate_buffers are non-blocking: the null stream does not wait for them)."""
+class _FramePreprocess:
+    """What the device pre-processes share: the source frame (pinned host +
+    device), an optional device LUT, run / fill_binding / free and the context
+    manager.  A subclass passes its geometry, the size of one output element
+    and its LUT to __init__ and implements _enqueue (one kernel, no sync)."""
 
-    def __init__(self, src_h: int, src_w: int, oh: int, ow: int, model: str, output: str = "float32_nchw",
-                 batch: int = 1):
-        if output not in OUTPUTS:
-            raise ValueError(f"output must be one of {OUTPUTS}, got {output!r}")
-        check_second_stage(model, int(oh), int(ow))
-        self.src = (int(src_h), int(src_w))
-        self.dst = (int(oh), int(ow))
+    def __init__(self, src_hw, dst_hw, batch: int, output: str, itemsize: int, lut: Optional[np.ndarray]):
+        self.src = (int(src_hw[0]), int(src_hw[1]))
+        self.dst = (int(dst_hw[0]), int(dst_hw[1]))
         self.batch = int(batch)
         self.output = output
-        self.mem: Optional[HostDeviceMem] = HostDeviceMem(self.batch * self.src[0] * self.src[1] * 3, np.uint8)
+        self.itemsize = int(itemsize)  # bytes of one output element
+        self.mem: Optional[HostDeviceMem] = None
         self.lut: Optional[HostDeviceMem] = None
-        if output == "float32_nchw":
-            try:
-                self.lut = HostDeviceMem(3 * 256, np.float32)
-                self.lut.host = normalize_lut(model)
+        try:
+            self.mem = HostDeviceMem(self.batch * self.src[0] * self.src[1] * 3, np.uint8)
+            if lut is not None:
+                self.lut = HostDeviceMem(lut.size, np.float32)
+                self.lut.host = np.ascontiguousarray(lut, dtype=np.float32)
                 _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(self.lut.device),
                           self.lut.host.ctypes.data_as(C.c_void_p), self.lut.nbytes, None)
                 _lib.call("mde_rt_device_synchronize")
-            except Exception:
-                self.free()
-                raise
+        except Exception:
+            self.free()
+            raise
+
+    def _enqueue(self, d_src: int, pitch: int, swap_rb: bool, d_dst: int, stream: int) -> None:
+        raise NotImplementedError
 
     def run_device(self, d_src: int, pitch: int, d_dst: int, stream: int, swap_rb: bool = True) -> None:
         """Frames already on the device: [batch][src_h][pitch] bytes, BGR unless swap_rb=False."""
         if self.mem is None:
-            raise RuntimeError("DevicePreprocess already freed")
-        resize_u8(d_src, self.batch, self.src[0], self.src[1], pitch, swap_rb, d_dst, self.dst[0], self.dst[1],
-                  stream, self.lut.device if self.lut is not None else 0)
+            raise RuntimeError(f"{type(self).__name__} already freed")
+        self._enqueue(d_src, pitch, swap_rb, d_dst, stream)
 
     def run(self, img_bgr: np.ndarray, d_dst: int, stream: int) -> None:
         if self.mem is None:
-            raise RuntimeError("DevicePreprocess already freed")
+            raise RuntimeError(f"{type(self).__name__} already freed")
         img = np.asarray(img_bgr)
         want = (self.batch, self.src[0], self.src[1], 3)
         if img.dtype != np.uint8 or img.shape not in (want, want[1:] if self.batch == 1 else want):
-            raise ValueError(f"DevicePreprocess.run wants a uint8 BGR array of shape {want}, got {img.dtype} "
+            raise ValueError(f"{type(self).__name__}.run wants a uint8 BGR array of shape {want}, got {img.dtype} "
                              f"{img.shape}")
         host = self.mem.host
         np.copyto(host.reshape(want), img.reshape(want))
@@ -207,7 +202,7 @@ class DevicePreprocess:
         bytes back into its pinned host side in stream order and synchronize:
         do_inference's own upload of `binding.host` then rewrites the device
         side with what is already there."""
-        need = self.batch * self.dst[0] * self.dst[1] * 3 * (4 if self.lut is not None else 1)
+        need = self.batch * self.dst[0] * self.dst[1] * 3 * self.itemsize
         if binding.nbytes < need:
             raise ValueError(f"binding holds {binding.nbytes} bytes, the {self.output} result needs {need}")
         self.run(img_bgr, binding.device, stream)
@@ -229,5 +224,119 @@ class DevicePreprocess:
         return False
 
 
+class DevicePreprocess(_FramePreprocess):
+    """Owns the source frame (pinned host + device) and the device LUT;
+    `run(img_bgr, d_dst, stream)` copies the frame to the device and enqueues
+    the resize straight into the engine's input binding `d_dst`:
+    output "float32_nchw" -> [batch][3][oh][ow] float32 (binding "input"),
+    "uint8_nhwc" -> [batch][oh][ow][3] uint8 RGB (binding "image_u8").
+    run() and run_device() only enqueue.  run() stages the frame in the one
+    pinned buffer this object owns and copies it from there asynchronously, so
+    the caller must synchronize `stream` (or otherwise know that copy has
+    finished) before the next run() overwrites the buffer; fill_binding() does.
+    The result is on the device in stream order: anything that reads `d_dst`
+    must be enqueued on `stream` or after a synchronize of it (the streams of
+    allocate_buffers are non-blocking: the null stream does not wait for them)."""
+
+    def __init__(self, src_h: int, src_w: int, oh: int, ow: int, model: str, output: str = "float32_nchw",
+                 batch: int = 1):
+        if output not in OUTPUTS:
+            raise ValueError(f"output must be one of {OUTPUTS}, got {output!r}")
+        check_second_stage(model, int(oh), int(ow))
+        f32 = output == "float32_nchw"
+        super().__init__((src_h, src_w), (oh, ow), batch, output, 4 if f32 else 1,
+                         normalize_lut(model) if f32 else None)
+
+    def _enqueue(self, d_src, pitch, swap_rb, d_dst, stream):
+        resize_u8(d_src, self.batch, self.src[0], self.src[1], pitch, swap_rb, d_dst, self.dst[0], self.dst[1],
+                  stream, self.lut.device if self.lut is not None else 0)
+
+
+# ---- Depth Pro -------------------------------------------------------------
+# Its pre-process is not the stretch above (and has no entry in SCALE_DTYPE):
+# reference models/depth_pro/onnx2trt.py:56-74 normalises first (ToTensor,
+# Normalize(0.5, 0.5)) and then resizes the float image with torch's bilinear,
+# align_corners=False.  The contract is spelled out in include/mde.h at
+# mde_op_dp_preprocess; resize_bilinear_f32 restates it in numpy float32, one
+# rounding per operation in the contract's order, and the kernel
+# (csrc/depth_pro_photo.hip) is held to it bit for bit.
+
+
+def depth_pro_lut() -> np.ndarray:
+    """float32 [256]: pixel value u after ToTensor and Normalize(0.5, 0.5),
+    ((float32(u) / 255) - 0.5) / 0.5 with every step in float32."""
+    u = np.arange(256, dtype=np.float32)
+    return ((u / np.float32(255)) - np.float32(0.5)) / np.float32(0.5)
+
+
+def _axis_lin(dst: int, src: int):
+    """Per output index of one axis: (i0, i1, l0, l1), float32 weights."""
+    f32 = np.float32
+    scale = f32(src) / f32(dst)
+    x = scale * (np.arange(dst, dtype=np.float32) + f32(0.5)) - f32(0.5)
+    x = np.maximum(x, f32(0))
+    i0 = np.minimum(x.astype(np.int64), src - 1)
+    i1 = np.minimum(i0 + 1, src - 1)
+    l1 = np.clip(x - i0.astype(np.float32), f32(0), f32(1))
+    l0 = f32(1) - l1
+    assert x.dtype == l0.dtype == l1.dtype == np.float32
+    return i0, i1, l0, l1
+
+
+def resize_bilinear_f32(img_chw_f32: np.ndarray, oh: int, ow: int) -> np.ndarray:
+    """`F.interpolate(img, (oh, ow), mode="bilinear", align_corners=False)`
+    for a float32 [..., H, W] image as the include/mde.h contract states it:
+    out = b0 * (a0 * v00 + a1 * v01) + b1 * (a0 * v10 + a1 * v11), float32
+    throughout.  The horizontal blend runs over whole source rows first; per
+    element that is the contract's operation order."""
+    img = np.asarray(img_chw_f32)
+    if img.dtype != np.float32 or img.ndim < 2:
+        raise ValueError(f"resize_bilinear_f32 wants a float32 [..., H, W] image, got {img.dtype} {img.shape}")
+    sh, sw = img.shape[-2:]
+    oh, ow = int(oh), int(ow)
+    if oh < 1 or ow < 1 or sh < 1 or sw < 1:
+        raise ValueError("resize_bilinear_f32: sizes must be positive")
+    x0, x1, a0, a1 = _axis_lin(ow, sw)
+    y0, y1, b0, b1 = _axis_lin(oh, sh)
+    rows = a0 * img[..., x0] + a1 * img[..., x1]  # [..., sh, ow]
+    out = b0[:, None] * rows[..., y0, :] + b1[:, None] * rows[..., y1, :]
+    assert out.dtype == np.float32
+    return out
+
+
+def preprocess_depth_pro_host(img_bgr: np.ndarray, size: int):
+    """BGR uint8 [H, W, 3] photo -> (float32 [1, 3, size, size] blob, (H, W)):
+    the reference's cvtColor(BGR2RGB), transform and F.interpolate on the host."""
+    img = np.asarray(img_bgr)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"preprocess_depth_pro_host wants a uint8 [H, W, 3] BGR image, got {img.dtype} {img.shape}")
+    x = depth_pro_lut()[img[:, :, ::-1]].transpose(2, 0, 1)
+    blob = np.ascontiguousarray(resize_bilinear_f32(x, int(size), int(size))[None])
+    return blob, (img.shape[0], img.shape[1])
+
+
+def dp_preprocess(d_src: int, batch: int, sh: int, sw: int, pitch: int, swap_rb: bool, d_lut: int, d_dst: int,
+                  oh: int, ow: int, stream: int = 0) -> None:
+    """Device pointers in/out, enqueued on `stream`: float32 NCHW out through `d_lut` (device float[256])."""
+    _lib.call("mde_op_dp_preprocess", C.c_void_p(int(d_src)), int(batch), int(sh), int(sw), int(pitch),
+              int(bool(swap_rb)), C.c_void_p(int(d_lut)), C.c_void_p(int(d_dst)), int(oh), int(ow),
+              C.c_void_p(int(stream or 0)))
+
+
+class DepthProPreprocess(_FramePreprocess):
+    """DevicePreprocess's counterpart for Depth Pro: owns the source frame
+    (pinned host + device) and the device LUT float[256]; run / run_device /
+    fill_binding write the engine's "input" binding, float32
+    [batch][3][size][size], under the same stream-order rules."""
+
+    def __init__(self, src_h: int, src_w: int, size: int, batch: int = 1):
+        super().__init__((src_h, src_w), (size, size), batch, "float32_nchw", 4, depth_pro_lut())
+
+    def _enqueue(self, d_src, pitch, swap_rb, d_dst, stream):
+        dp_preprocess(d_src, self.batch, self.src[0], self.src[1], pitch, swap_rb, self.lut.device, d_dst,
+                      self.dst[0], self.dst[1], stream)
+
+
 __all__ = ["resize_linear_u8", "normalize_lut", "preprocess_host", "load_image_bgr", "resize_u8",
-           "DevicePreprocess", "check_second_stage"]
+           "DevicePreprocess", "check_second_stage", "depth_pro_lut", "resize_bilinear_f32",
+           "preprocess_depth_pro_host", "dp_preprocess", "DepthProPreprocess"]
