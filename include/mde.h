@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MDE_ABI_VERSION 10
+#define MDE_ABI_VERSION 11
 
 typedef enum {
   MDE_OK = 0,
@@ -279,6 +279,57 @@ int mde_op_resize_bilinear(const void* in_f16, int batch, int ih, int iw, int c,
 int mde_op_depth_head(const void* in_f16, int batch, int sh, int sw, int cin, int uh, int uw, const void* w_f16,
                       int ldw, const float* bias, const float* w2, float b2, int metric, float max_depth,
                       float* out_f32, void* stream);
+/* ---- since ABI 11: the GEMM / conv options that only the engine graphs set, one thin test surface
+ * each (no reference counterpart; tests/test_gpu_ops_engine_paths.py).  No policy of their own: the
+ * launcher picks the route exactly as it does for the engines.
+ *
+ * Fused split-K operands, shared by three of them: tile_cnt (optional) = tile_cnt_cap zero-initialised
+ * int counters, at least one per 64 x 64 output tile, left zero by every call; slot_floats = the part of
+ * ws (<= ws_floats) the one-launch form may use for its per-tile slots.  With the switch "splitk_fused"
+ * on and room for slices x tiles x tile area floats the split runs as one launch, otherwise as slices +
+ * a reduce kernel -- the same sums in the same order. */
+/* mde_op_linear_ws plus the E_STORE residual options: out = act(a W^T + bias) + r0 + res1, where r0 =
+ * res0[m] (res0_rows == 0: res0 is [m][ldo]) or res0[m % res0_rows] (res0 is a [res0_rows][ldo] table,
+ * VGGT's per-image positional embedding), through a ReLU when res0_relu (VGGT's in-place-ReLU residual
+ * units).  res0 and res1 use the output's row stride ldo. */
+int mde_op_linear_res(const void* a_f16, int lda, const void* w_f16, int ldw, int m, int n, int k, const float* bias,
+                      int act, const void* res0_f16, int res0_rows, int res0_relu, const void* res1_f16,
+                      void* out_f16, int ldo, float* ws, size_t ws_floats, int* slices, int* tile_cnt,
+                      int tile_cnt_cap, size_t slot_floats, void* stream);
+/* mde_op_conv3x3_ws plus res0_relu and res1_up: with res1_up_f16 [batch][res1_uh][res1_uw][cout] set,
+ * res1 is its bilinear (align_corners=True) upsample to the output map -- read on the fly by the
+ * direct conv's epilogue (switch "resize_fold"), or first written into res1_f16, which must be a
+ * buffer of the output's shape either way. */
+int mde_op_conv3x3_res(const void* in_f16, int batch, int h, int w, int cin, const void* w_f16, int ldw, int cout,
+                       int stride, int relu_in, const float* bias, int act, const void* res0_f16, int res0_relu,
+                       const void* res1_f16, const void* res1_up_f16, int res1_uh, int res1_uw, void* out_f16,
+                       float* ws, size_t ws_floats, int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats,
+                       void* stream);
+/* mde_op_linear_lnfold reading the residual stream past every sequence's cls row (the DPT projects):
+ * x [seqs*tokens][k] and ln_partials [k/32][seqs*tokens][2] cover all rows, out has seqs*(tokens-1)
+ * rows; output row r reads row (r / (tokens-1)) * tokens + 1 + r % (tokens-1).  tokens >= 2. */
+int mde_op_linear_lnfold_tok(const void* x_f16, const float* ln_partials, float eps, const void* wg_f16, int ldw,
+                             const float* c1, const float* c2, int seqs, int tokens, int n, int k, int act,
+                             void* out_f16, int ldo, void* stream);
+/* mde_op_depth_head with hpe_f16 (optional) [hpe_pix][32] added to the hidden layer before its ReLU at
+ * output pixel m % hpe_pix (VGGT: the folded conv of the UV positional embedding).  metric: 0 ReLU,
+ * 1 max_depth * sigmoid, 2 exp. */
+int mde_op_depth_head_pe(const void* in_f16, int batch, int sh, int sw, int cin, int uh, int uw, const void* w_f16,
+                         int ldw, const float* bias, const float* w2, float b2, int metric, float max_depth,
+                         const void* hpe_f16, int hpe_pix, float* out_f32, void* stream);
+/* mde_op_conv_transpose into a channel slot of a wider NHWC map (the DPT / Depth Pro concat buffers):
+ * ldo = channels of that map (>= cout), out_f16 = its base + the slot's first channel.  cout % 8 ==
+ * 0, ldo % 8 == 0 and out_f16 16-B aligned (every store is 16 B). */
+int mde_op_conv_transpose_ld(const void* in_f16, int batch, int h, int w, int cin, const void* w_f16, int ldw,
+                             int cout, int stride, const float* bias, void* out_f16, int ldo, void* stream);
+/* mde_op_linear_residual (x32) / mde_op_linear_residual_f16 (xh_f16, optional ln_partials) -- exactly
+ * one of x32 and xh_f16 -- with the K loop cut into slices when splitk > 1 (small grids with a long
+ * K: the batch-1 fc2).  ws holds the slices' fp32 partial sums: the route on 128 x 128 tiles takes 4
+ * slices whatever splitk says, so ws must hold max(splitk, 4) * m * n floats.  splitk <= 1: unsplit. */
+int mde_op_linear_residual_split(const void* a_f16, int lda, const void* w_f16, int ldw, int m, int n, int k,
+                                 const float* bias, const float* layer_scale, float* x32, void* xh_f16, int ldx,
+                                 float* ln_partials, int splitk, float* ws, size_t ws_floats, int* tile_cnt,
+                                 int tile_cnt_cap, size_t slot_floats, void* stream);
 /* uint8 NHWC image [batch][h][w][3] -> the patch-embed operand [batch*(h/14)*(w/14)][672] f16
  * (patch-major, channel, row, 16-wide padded column), computing ((float)u / scale - mean[c]) / std[c]
  * in fp32 (the ONNX preamble of reference core/onnx_tools.py:175-199: Cast, Div, Sub, Div). */

@@ -143,6 +143,21 @@ PROTOTYPES = {
     "mde_op_resize_bilinear": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     "mde_op_depth_head": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                           c_void_p, c_float, c_int, c_float, c_void_p, c_void_p],
+    "mde_op_linear_res": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                          c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, P(c_int), c_void_p, c_int, c_size_t,
+                          c_void_p],
+    "mde_op_conv3x3_res": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                           c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                           P(c_int), c_void_p, c_int, c_size_t, c_void_p],
+    "mde_op_linear_lnfold_tok": [c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_int, c_int, c_void_p, c_int, c_void_p],
+    "mde_op_depth_head_pe": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                             c_void_p, c_float, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p],
+    "mde_op_conv_transpose_ld": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, c_int, c_void_p],
+    "mde_op_linear_residual_split": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
+                                     c_int, c_size_t, c_void_p],
     "mde_op_patch_prep_u8": [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "mde_op_dp_pyramid_patches": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "mde_op_merge_tokens": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,

@@ -1935,4 +1935,201 @@ int mde_op_depth_head(const void* in, int batch, int sh, int sw, int cin, int uh
   OP_RET(launch_gemm(g, (hipStream_t)st), "depth_head");
 }
 
+// ---- the GemmParams options only the engine graphs set, one wrapper each ----
+// (no kernel code and no policy here: launch_gemm picks the route as it does
+// for the engines; tests/test_gpu_ops_engine_paths.py)
+namespace {
+// fused split-K operands (GemmParams::tile_cnt): the slots live in ws, and
+// every 64^2 tile of the problem has a counter (the 128^2 grids are smaller)
+const char* fused_split_error(const float* ws, size_t ws_floats, const int* tile_cnt, int tile_cnt_cap,
+                              size_t slot_floats, int m, int n) {
+  if (!tile_cnt) return nullptr;
+  if (!ws || slot_floats > ws_floats) return "fused split-K: slot_floats exceeds the workspace";
+  const long long t64 = (long long)((m + 63) / 64) * ((n + 63) / 64);
+  if (tile_cnt_cap < t64) return "fused split-K: fewer counters than 64^2 tiles";
+  return nullptr;
+}
+}  // namespace
+
+int mde_op_linear_res(const void* a, int lda, const void* wt, int ldw, int m, int n, int k, const float* bias, int act,
+                      const void* res0, int res0_rows, int res0_relu, const void* res1, void* out, int ldo, float* ws,
+                      size_t ws_floats, int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats, void* st) {
+  if (!a || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
+  if (res0_rows < 0 || ((res0_rows > 0 || res0_relu) && !res0)) return fail(MDE_ERR_ARG, "res0 options without res0");
+  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, m, n))
+    return fail(MDE_ERR_ARG, why);
+  GemmParams g;
+  g.A = (const h16*)a;
+  g.lda = lda;
+  g.W = (const h16*)wt;
+  g.ldw = ldw;
+  g.M = m;
+  g.N = n;
+  g.K = k;
+  g.bias = bias;
+  g.act = act;
+  g.res0 = (const h16*)res0;
+  g.res0_rows = res0_rows;
+  g.res0_relu = res0_relu ? 1 : 0;
+  g.res1 = (const h16*)res1;
+  g.out16 = (h16*)out;
+  g.ldo = ldo;
+  g.partial = ws;
+  g.partial_cap = ws_floats;
+  g.tile_cnt = tile_cnt;
+  g.tile_cnt_cap = tile_cnt_cap;
+  g.slot_cap = slot_floats;
+  if (slices) *slices = gemm_store_split_slices(g);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_res");
+}
+
+int mde_op_conv3x3_res(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout, int stride,
+                       int relu_in, const float* bias, int act, const void* res0, int res0_relu, const void* res1,
+                       const void* res1_up, int res1_uh, int res1_uw, void* out, float* ws, size_t ws_floats,
+                       int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats, void* st) {
+  if (!in || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
+  if (stride != 1 && stride != 2) return fail(MDE_ERR_ARG, "stride must be 1 or 2");
+  if (res0_relu && !res0) return fail(MDE_ERR_ARG, "res0_relu without res0");
+  if (res1_up && !res1) return fail(MDE_ERR_ARG, "res1_up needs res1 (a buffer of the output's shape)");
+  GemmParams g = conv3x3_params(in, batch, h, w, cin, wt, ldw, cout, stride, relu_in, bias, act, res0, res1, out);
+  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, g.M, g.N))
+    return fail(MDE_ERR_ARG, why);
+  g.res0_relu = res0_relu ? 1 : 0;
+  g.res1_up = (const h16*)res1_up;
+  g.res1_uh = res1_uh;
+  g.res1_uw = res1_uw;
+  g.partial = ws;
+  g.partial_cap = ws_floats;
+  g.tile_cnt = tile_cnt;
+  g.tile_cnt_cap = tile_cnt_cap;
+  g.slot_cap = slot_floats;
+  if (slices) *slices = gemm_store_split_slices(g);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "conv3x3_res");
+}
+
+int mde_op_linear_lnfold_tok(const void* x, const float* ln_partials, float eps, const void* wg, int ldw,
+                             const float* c1, const float* c2, int seqs, int tokens, int n, int k, int act, void* out,
+                             int ldo, void* st) {
+  if (!x || !ln_partials || !wg || !c1 || !c2 || !out) return fail(MDE_ERR_ARG, "null argument");
+  if (k & 31) return fail(MDE_ERR_ARG, "k % 32 != 0");
+  if (seqs < 1 || tokens < 2) return fail(MDE_ERR_ARG, "seqs >= 1 and tokens >= 2 (a cls row and at least one more)");
+  GemmParams g;
+  g.A = (const h16*)x;
+  g.lda = k;
+  g.W = (const h16*)wg;
+  g.ldw = ldw;
+  g.M = seqs * (tokens - 1);
+  g.N = n;
+  g.K = k;
+  g.bias = c2;
+  g.act = act;
+  g.out16 = (h16*)out;
+  g.ldo = ldo;
+  g.lnst_in = ln_partials;
+  g.lnc1 = c1;
+  g.lnst_ns = k / 32;
+  g.lnst_rows = seqs * tokens;
+  g.ln_eps = eps;
+  g.a_tok = tokens;
+  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_lnfold_tok");
+}
+
+int mde_op_depth_head_pe(const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt, int ldw,
+                         const float* bias, const float* w2, float b2, int metric, float max_depth, const void* hpe,
+                         int hpe_pix, float* out, void* st) {
+  if (!in || !wt || !bias || !w2 || !out) return fail(MDE_ERR_ARG, "null argument");
+  if (hpe && hpe_pix < 1) return fail(MDE_ERR_ARG, "hpe needs hpe_pix >= 1");
+  GemmParams g;
+  g.amode = A_CONV3_UP;
+  g.emode = E_HEAD;
+  g.A = (const h16*)in;
+  g.cb = batch;
+  g.ch = sh;
+  g.cw = sw;
+  g.cc = cin;
+  g.uh = uh;
+  g.uw = uw;
+  g.oh = uh;
+  g.ow = uw;
+  g.stride = 1;
+  g.W = (const h16*)wt;
+  g.ldw = ldw;
+  g.M = batch * uh * uw;
+  g.N = 32;
+  g.K = 9 * cin;
+  g.bias = bias;
+  g.w2 = w2;
+  g.b2 = b2;
+  g.head_metric = metric;
+  g.max_depth = max_depth;
+  g.hpe = (const h16*)hpe;
+  g.hpe_pix = hpe ? hpe_pix : 0;
+  g.out32 = out;
+  OP_RET(launch_gemm(g, (hipStream_t)st), "depth_head_pe");
+}
+
+int mde_op_conv_transpose_ld(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout,
+                             int stride, const float* bias, void* out, int ldo, void* st) {
+  if (!in || !wt || !bias || !out) return fail(MDE_ERR_ARG, "null argument");
+  GemmParams g;
+  g.emode = E_CONVT;
+  g.A = (const h16*)in;
+  g.lda = cin;
+  g.W = (const h16*)wt;
+  g.ldw = ldw;
+  g.M = batch * h * w;
+  g.N = stride * stride * cout;
+  g.K = cin;
+  g.bias = bias;
+  g.out16 = (h16*)out;
+  g.s = stride;
+  g.cout = cout;
+  g.ldo = ldo;
+  g.ih = h;
+  g.iw = w;
+  OP_RET(launch_gemm(g, (hipStream_t)st), "conv_transpose_ld");
+}
+
+int mde_op_linear_residual_split(const void* a, int lda, const void* wt, int ldw, int m, int n, int k,
+                                 const float* bias, const float* ls, float* x32, void* xh, int ldx, float* ln_partials,
+                                 int splitk, float* ws, size_t ws_floats, int* tile_cnt, int tile_cnt_cap,
+                                 size_t slot_floats, void* st) {
+  if (!a || !wt || !bias || !ls || (!x32 == !xh) || (!ws && ws_floats))
+    return fail(MDE_ERR_ARG, "null argument (one of x32 / xh)");
+  if (ln_partials && (!xh || (n & 31))) return fail(MDE_ERR_ARG, "ln_partials need xh and n % 32 == 0");
+  if (m < 0 || n < 0 || splitk < 0) return fail(MDE_ERR_ARG, "negative size");
+  // the 128^2 route cuts K into 4 slices whatever splitk says
+  if (splitk > 1 && (!ws || ws_floats / (size_t)(splitk > 4 ? splitk : 4) < (size_t)m * (size_t)n))
+    return fail(MDE_ERR_ARG, "ws must hold max(splitk, 4) * m * n floats");
+  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, m, n))
+    return fail(MDE_ERR_ARG, why);
+  GemmParams g;
+  g.emode = E_RESID;
+  g.A = (const h16*)a;
+  g.lda = lda;
+  g.W = (const h16*)wt;
+  g.ldw = ldw;
+  g.M = m;
+  g.N = n;
+  g.K = k;
+  g.bias = bias;
+  g.ls = ls;
+  g.x32 = x32;
+  g.xh = (h16*)xh;
+  g.ldo = ldx;
+  if (ln_partials) {
+    g.lnst_out = ln_partials;
+    g.lnst_ns = n / 32;
+    g.lnst_rows = m;
+  }
+  if (splitk > 1) {
+    g.splitk = splitk;
+    g.partial = ws;
+    g.tile_cnt = tile_cnt;
+    g.tile_cnt_cap = tile_cnt_cap;
+    g.slot_cap = slot_floats;
+  }
+  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual_split");
+}
+
 }  // extern "C"

@@ -23,7 +23,7 @@ enum Knob : int {
   // test_conv_narrow_tiles_bit_exact
   KNOB_CONV_NARROW,
   // separable upsampling conv for the 32-channel head convs (1: on).
-  // test_upconv_matches_conv3
+  // test_upconv_matches_conv3, test_depth_head_pe (op level: hpe, exp)
   KNOB_UPCONV,
   // 256^2 phase-pipelined GEMM for large long-K problems (0 never, 1 auto, 2
   // whenever legal).  test_gemm256_modes_match
@@ -36,7 +36,7 @@ enum Knob : int {
   KNOB_W8SMALL,
   // persistent 64 -> 64 channel direct conv with LDS-resident weights (0 off,
   // 1: 16 x 16-pixel tiles on 8 waves, 2: 8 x 16 on 4 waves).
-  // test_conv_persist_bit_exact
+  // test_conv_persist_bit_exact, test_conv_res0_relu_persist (op level: res0_relu)
   KNOB_CONV_PERSIST,
   // A-stationary panel GEMM (gemm_panel.hip) for the K = 384 E_STORE /
   // E_QKV problems at large batch -- the ViT-S fc1 and qkv (1: on; 2: also
@@ -49,7 +49,8 @@ enum Knob : int {
   KNOB_PANEL32,
   // small-grid residual updates (ViT-S batch 1: fc2 / proj, 1370 x 384) on
   // 32 x 64 tiles with the whole K loop and a 4-deep ring instead of split-K
-  // slices + the reduce launch (1: on).  test_narrow_resid_matches_split
+  // slices + the reduce launch (1: on).  test_narrow_resid_matches_split,
+  // test_residual_splitk (op level)
   KNOB_NARROW_RESID,
   // the large-grid attention (8 waves, unsplit: B = 48) on
   // v_mfma_f32_16x16x32_f16 (attn16_fwd_kernel; 1: on; 0: the 32x32x16
@@ -59,7 +60,8 @@ enum Knob : int {
   // the last slice of a tile to arrive adds the slots in slice order and runs
   // the epilogue; 1: on; 0, the default: slices + splitk_resid / splitk_store
   // kernels -- the fused tail's system-scope round trips measured slower,
-  // ViT-L B=1 3.17 -> 3.79 ms).  test_splitk_fused_matches_two_kernel
+  // ViT-L B=1 3.17 -> 3.79 ms).  test_splitk_fused_matches_two_kernel,
+  // test_residual_splitk, test_linear_res_split_store, test_conv_res0_relu (op level, bit for bit)
   KNOB_SPLITK_FUSED,
   // attn16's partial last query block of every sequence dispatched after all
   // full blocks (1: work order only, bit-identical; 2, the default: and a
@@ -70,7 +72,7 @@ enum Knob : int {
   // the DPT fusion blocks' x2 resize read on the fly by the next block's
   // residual conv (GemmParams::res1_up: the direct conv's epilogue blends the
   // four taps) instead of a resize launch (1: on).  Same bits.
-  // test_resize_fold_bit_exact
+  // test_resize_fold_bit_exact, test_conv_res1_up (op level, against torch)
   KNOB_RESIZE_FOLD,
   KNOB_COUNT
 };

@@ -153,3 +153,53 @@ def test_qkv_ops_reject_bad_geometry(lib_path, tpad, heads, msg):
     assert rc != 0 and msg in lib.mde_last_error()
     rc = lib.mde_op_qkv_lnfold(p, p, 1e-6, p, 384, p, p, 1, 37, heads, tpad, 0.125, p, p, p, None)
     assert rc != 0 and msg in lib.mde_last_error()
+
+
+def test_engine_path_wrappers_reject_bad_arguments(lib_path):
+    """The ABI 11 wrappers (mde_op_linear_res, ..., mde_op_linear_residual_split) answer null
+    pointers, tokens < 2, a misaligned ConvT slot and fused split-K operands that do not fit before
+    any kernel launch (the pointers below are never dereferenced)."""
+    from monocular_depth_estimation_trt_amd import _lib
+    L = _lib.lib()
+    p = 4096
+
+    def err(rc, msg):
+        assert rc == 1, (rc, L.mde_last_error())
+        assert msg in L.mde_last_error(), L.mde_last_error()
+
+    err(L.mde_op_linear_res(None, 72, p, 128, 185, 96, 72, p, 0, None, 0, 0, None, p, 96, None, 0, None, None, 0, 0,
+                            None), b"null")
+    err(L.mde_op_linear_res(p, 72, p, 128, 185, 96, 72, p, 0, None, 37, 0, None, p, 96, None, 0, None, None, 0, 0,
+                            None), b"without res0")
+    # 185 x 96 has 3 x 2 tiles of 64^2: one counter is too few; slots past the workspace
+    err(L.mde_op_linear_res(p, 768, p, 768, 185, 96, 768, p, 0, None, 0, 0, None, p, 96, p, 1 << 18, None, p, 1, 1 << 18,
+                            None), b"fewer counters")
+    err(L.mde_op_linear_res(p, 768, p, 768, 185, 96, 768, p, 0, None, 0, 0, None, p, 96, p, 1 << 10, None, p, 64,
+                            1 << 18, None), b"exceeds the workspace")
+    err(L.mde_op_conv3x3_res(p, 1, 19, 19, 384, p, 3456, 64, 1, 0, p, 0, None, 0, None, None, 0, 0, None, None, 0, None,
+                             None, 0, 0, None), b"null")
+    err(L.mde_op_conv3x3_res(p, 1, 19, 19, 384, p, 3456, 64, 1, 0, p, 0, None, 1, None, None, 0, 0, p, None, 0, None,
+                             None, 0, 0, None), b"res0_relu without res0")
+    err(L.mde_op_conv3x3_res(p, 1, 19, 19, 384, p, 3456, 64, 1, 0, p, 0, None, 0, None, p, 10, 10, p, None, 0, None,
+                             None, 0, 0, None), b"res1_up needs res1")
+    err(L.mde_op_conv3x3_res(p, 1, 19, 19, 384, p, 3456, 64, 1, 0, p, 0, None, 0, None, None, 0, 0, p, p, 1 << 20, None,
+                             p, 5, 1 << 20, None), b"fewer counters")
+    err(L.mde_op_linear_lnfold_tok(p, None, 1e-6, p, 384, p, p, 7, 38, 48, 384, 0, p, 48, None), b"null")
+    err(L.mde_op_linear_lnfold_tok(p, p, 1e-6, p, 384, p, p, 7, 1, 48, 384, 0, p, 48, None), b"tokens >= 2")
+    err(L.mde_op_depth_head_pe(p, 1, 8, 8, 32, 16, 16, p, 320, p, p, 0.0, 2, 1.0, p, 0, p, None), b"hpe_pix")
+    err(L.mde_op_depth_head_pe(p, 1, 8, 8, 32, 16, 16, p, 320, p, None, 0.0, 2, 1.0, None, 0, p, None), b"null")
+    err(L.mde_op_conv_transpose_ld(p, 1, 7, 9, 64, p, 64, 64, 2, p, None, 80, None), b"null")
+    # a slot 8 bytes into the pixel (every store is 16 B), a stride below cout, a stride off 8
+    err(L.mde_op_conv_transpose_ld(p, 1, 7, 9, 64, p, 64, 64, 2, p, p + 8, 80, None), b"conv_transpose_ld")
+    err(L.mde_op_conv_transpose_ld(p, 1, 7, 9, 64, p, 64, 64, 2, p, p, 56, None), b"conv_transpose_ld")
+    err(L.mde_op_conv_transpose_ld(p, 1, 7, 9, 64, p, 64, 64, 2, p, p, 84, None), b"conv_transpose_ld")
+    rs = L.mde_op_linear_residual_split
+    err(rs(p, 1536, p, 1536, 300, 384, 1536, p, p, p, p, 384, None, 4, p, 1 << 22, None, 0, 0, None), b"one of x32 / xh")
+    err(rs(p, 1536, p, 1536, 300, 384, 1536, p, p, None, None, 384, None, 4, p, 1 << 22, None, 0, 0, None),
+        b"one of x32 / xh")
+    err(rs(p, 1536, p, 1536, 300, 384, 1536, p, p, p, None, 384, p, 4, p, 1 << 22, None, 0, 0, None), b"ln_partials")
+    # 2 slices asked: the workspace must still hold 4 x 300 x 384 floats
+    err(rs(p, 1536, p, 1536, 300, 384, 1536, p, p, p, None, 384, None, 2, p, 2 * 300 * 384, None, 0, 0, None),
+        b"max(splitk, 4)")
+    err(rs(p, 1536, p, 1536, 300, 384, 1536, p, p, p, None, 384, None, 4, p, 1 << 22, p, 29, 1 << 22, None),
+        b"fewer counters")
