@@ -20,7 +20,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libmde_hip.so")
 OBJDIR = os.path.join(ROOT, "build", "obj")
 ARCH = os.environ.get("MDE_OFFLOAD_ARCH", "gfx950")
-SOURCES = ["gemm.hip", "conv.hip", "attention.hip", "elementwise.hip", "engine.hip",
+SOURCES = ["gemm.hip", "conv.hip", "attention.hip", "elementwise.hip", "engine.hip", "ops_abi.hip",
            "depth_pro.hip", "depth_pro_ops.hip", "gemm256.hip", "gemm_panel.hip", "vggt.hip", "vggt_ops.hip", "tuning.hip", "fp32.hip",
            "preprocess.hip", "depth_pro_photo.hip"]
 # attention / conv: no NaN inputs by construction (masked keys are -inf, never

@@ -205,62 +205,22 @@ void Runner::dp_encoder(const std::string& pfx, float* X, const h16* P, int nseq
     snprintf(nm, sizeof nm, "%spatch_embed", pfx.c_str());
     gemm(nm, g);
   }
+  VitBlock blk;  // fp32 residual, LayerNorm launches, no fc2 split-K workspace
+  blk.seqs = nseq;
+  blk.T = T;
+  blk.Tpad = e.Tpad;
+  blk.eps = cf.ln_eps;
+  blk.X = X;
+  blk.Hn = d.Hn;
+  blk.Q = d.Q;
+  blk.K = d.K;
+  blk.Vt = d.Vt;
+  blk.O = d.O;
+  blk.Mh = d.Mh;
   for (int i = 0; i < cf.depth; ++i) {
-    const std::string p = pfx + "b" + std::to_string(i) + ".";
-    snprintf(nm, sizeof nm, "%sblock%d.norm1", pfx.c_str(), i);
-    step(nm, [&] {
-      return launch_layernorm(X, d.Hn, w32(p + "ln1.g"), w32(p + "ln1.b"), nseq * T, D, cf.ln_eps, T, 0, st);
-    });
-    {
-      GemmParams g = dense(d.Hn, D, p + "qkv.w", nseq * T, 3 * D, D);
-      g.emode = E_QKV;
-      g.bias = w32(p + "qkv.b");
-      g.q = d.Q;
-      g.k = d.K;
-      g.vt = d.Vt;
-      g.T = T;
-      g.Tpad = e.Tpad;
-      g.heads = e.H;
-      g.qscale = 0.125f * 1.4426950408889634f;  // dh^-0.5 * log2(e)
-      snprintf(nm, sizeof nm, "%sblock%d.qkv", pfx.c_str(), i);
-      gemm(nm, g);
-    }
-    snprintf(nm, sizeof nm, "%sblock%d.attn", pfx.c_str(), i);
-    step(nm, [&] { return launch_attention(d.Q, d.K, d.Vt, d.O, nseq, e.H, T, e.Tpad, D, st); });
-    {
-      GemmParams g = dense(d.O, D, p + "proj.w", nseq * T, D, D);
-      g.emode = E_RESID;
-      g.bias = w32(p + "proj.b");
-      g.ls = w32(p + "ls1");
-      g.x32 = X;
-      g.ldo = D;
-      snprintf(nm, sizeof nm, "%sblock%d.proj", pfx.c_str(), i);
-      gemm(nm, g);
-    }
-    snprintf(nm, sizeof nm, "%sblock%d.norm2", pfx.c_str(), i);
-    step(nm, [&] {
-      return launch_layernorm(X, d.Hn, w32(p + "ln2.g"), w32(p + "ln2.b"), nseq * T, D, cf.ln_eps, T, 0, st);
-    });
-    {
-      GemmParams g = dense(d.Hn, D, p + "fc1.w", nseq * T, cf.mlp_hidden, D);
-      g.emode = E_STORE;
-      g.bias = w32(p + "fc1.b");
-      g.act = ACT_GELU;
-      g.out16 = d.Mh;
-      g.ldo = cf.mlp_hidden;
-      snprintf(nm, sizeof nm, "%sblock%d.fc1", pfx.c_str(), i);
-      gemm(nm, g);
-    }
-    {
-      GemmParams g = dense(d.Mh, cf.mlp_hidden, p + "fc2.w", nseq * T, D, cf.mlp_hidden);
-      g.emode = E_RESID;
-      g.bias = w32(p + "fc2.b");
-      g.ls = w32(p + "ls2");
-      g.x32 = X;
-      g.ldo = D;
-      snprintf(nm, sizeof nm, "%sblock%d.fc2", pfx.c_str(), i);
-      gemm(nm, g);
-    }
+    blk.w = pfx + "b" + std::to_string(i) + ".";
+    blk.name = pfx + "block" + std::to_string(i) + ".";
+    vit_block(blk);
     for (int k = 0; k < 2 && hook_seqs > 0; ++k) {
       if (cf.hooks[k] != i) continue;
       DpMerge m;

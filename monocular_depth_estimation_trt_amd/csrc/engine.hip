@@ -1,7 +1,8 @@
 // libmde_hip engine: packed-weight loader, execution context and the DA-V2
-// forward schedule, behind the C ABI of include/mde.h.  The Depth Pro
+// forward schedule, behind the C ABI of include/mde.h, with the steps the
+// families share (Runner::vit_block, the DPT decoder's dpt_*).  The Depth Pro
 // schedule lives in depth_pro.hip, VGGT's in vggt.hip; all share
-// engine_internal.h.
+// engine_internal.h.  The op-level entry points (mde_op_*) are in ops_abi.hip.
 //
 // Replaces TensorRT's ICudaEngine / IExecutionContext as used by the
 // reference (core/common.py:141-312, core/common_runtime.py:131-275): one
@@ -19,18 +20,20 @@
 using namespace mde;
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
 
-int fail(int code, const std::string& msg) {
+int mde::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-int hip_fail(hipError_t e, const char* what) {
+int mde::hip_fail(hipError_t e, const char* what) {
   g_err = std::string(what) + ": " + hipGetErrorString(e);
   return MDE_ERR_HIP;
 }
+
+namespace {
 
 #define HIP_OR(call, what)                         \
   do {                                             \
@@ -175,6 +178,29 @@ namespace mde {
 // unfolded linears (A/B, tests); read when a context is created
 bool lnfold_off() { return knob(KNOB_LNFOLD) == 0; }
 
+DptMaps plan_dpt_maps(ArenaPlan& a, size_t n, const mde_engine& e) {
+  const size_t F = e.F, np = e.np;
+  const int* oc = e.cfg.out_channels;
+  const size_t s0 = (size_t)(8 * e.ph) * (8 * e.pw), s1 = (size_t)(4 * e.ph) * (4 * e.pw),
+               s2 = (size_t)(2 * e.ph) * (2 * e.pw), s3 = np, s4 = (size_t)e.h4 * e.w4;
+  const size_t ss[4] = {s1, s2, s3, s4};
+  DptMaps m{};
+  for (int i = 0; i < 4; ++i) m.pj[i] = a.h(n * np * oc[i]);
+  m.l1 = a.h(n * s1 * e.c1p);  // channels padded to a multiple of 32 (pad stays 0)
+  m.l2 = a.h(n * s2 * oc[1]);
+  m.l4 = a.h(n * s4 * oc[3]);
+  for (int i = 0; i < 4; ++i) m.rn[i] = a.h(n * ss[i] * F);
+  m.tb = a.h(n * s1 * F);
+  m.sb = a.h(n * s1 * F);
+  m.ub = a.h(n * s1 * F);
+  m.vb = a.h(n * s1 * F);
+  m.p4 = a.h(n * s3 * F);
+  m.p3 = a.h(n * s2 * F);
+  m.p2 = a.h(n * s1 * F);
+  m.c1 = a.h(n * s0 * (F / 2));
+  return m;
+}
+
 size_t plan_arena_dav2(const mde_engine& e, int B, DAV2Buf* b, uint8_t* base) {
   ArenaPlan a(base);
   const size_t bb = (size_t)B;
@@ -227,19 +253,7 @@ size_t plan_arena_dav2(const mde_engine& e, int B, DAV2Buf* b, uint8_t* base) {
   const size_t ss[4] = {s1, s2, s3, s4};
   if (!e.head_f32) {
     for (int i = 0; i < 4; ++i) t.tap[i] = fold_taps ? nullptr : a.h(bb * np * D);
-    for (int i = 0; i < 4; ++i) t.pj[i] = a.h(bb * np * oc[i]);
-    t.l1 = a.h(bb * s1 * e.c1p);  // channels padded to a multiple of 32 (pad stays 0)
-    t.l2 = a.h(bb * s2 * oc[1]);
-    t.l4 = a.h(bb * s4 * oc[3]);
-    for (int i = 0; i < 4; ++i) t.rn[i] = a.h(bb * ss[i] * F);
-    t.tb = a.h(bb * s1 * F);
-    t.sb = a.h(bb * s1 * F);
-    t.ub = a.h(bb * s1 * F);
-    t.vb = a.h(bb * s1 * F);
-    t.p4 = a.h(bb * s3 * F);
-    t.p3 = a.h(bb * s2 * F);
-    t.p2 = a.h(bb * s1 * F);
-    t.c1 = a.h(bb * s0 * (F / 2));
+    t.m = plan_dpt_maps(a, bb, e);
   } else {
     // exact-fp32 DPT head: the same maps in fp32 (l1 unpadded: the fp32 conv
     // takes any channel count % 4), plus the upsampled head inputs
@@ -296,26 +310,144 @@ namespace mde {
 // "resize_fold"; GemmParams::res1_up), or written into x0 by that launch when
 // its conv route cannot.  Returns true when this block's own resize into dst
 // is left to the next block that way.
-bool Runner::dav2_fusion(int r, const h16* x0, const h16* x1, int B, int h, int w, h16* dst, int oh, int ow,
-                         const h16* x0_up, int uh, int uw) {
+// relu_res: residual units with in-place ReLUs, whose skips add relu(x)
+// (VGGT's DPT head).  The block is refinenet r: its inputs, size and
+// destination follow from r.
+bool Runner::dpt_fusion(DptMaps& m, int n, int r, bool relu_res, bool fold_resize, const h16* x0_up, int uh, int uw) {
   const std::string p = "rf" + std::to_string(r);
-  const int F = c.e->F;
+  const int F = c.e->F, h = dpt_h(r - 1), w = dpt_w(r - 1);
+  const h16* x0 = r == 4 ? m.rn[3] : r == 3 ? m.p4 : r == 2 ? m.p3 : m.p2;
+  const h16* x1 = r == 4 ? nullptr : m.rn[r - 1];
+  h16* dst = r == 4 ? m.p4 : r == 3 ? m.p3 : r == 2 ? m.p2 : nullptr;  // r == 1: the 1x1 result stays in vb
   const h16* s = x0;
   if (x1) {
-    rcu(p + ".rcu1", x1, x0, c.b.sb, c.b.tb, B, h, w, F, false, x0_up, uh, uw);
-    s = c.b.sb;
+    rcu(p + ".rcu1", x1, x0, m.sb, m.tb, n, h, w, F, relu_res, x0_up, uh, uw);
+    s = m.sb;
   }
-  rcu(p + ".rcu2", s, nullptr, c.b.ub, c.b.tb, B, h, w, F);
-  GemmParams g = dense(c.b.ub, F, p + ".out.w", B * h * w, F, F);
+  rcu(p + ".rcu2", s, nullptr, m.ub, m.tb, n, h, w, F, relu_res);
+  GemmParams g = dense(m.ub, F, p + ".out.w", n * h * w, F, F);
   g.emode = E_STORE;
   g.bias = w32(p + ".out.b");
-  g.out16 = c.b.vb;
+  g.out16 = m.vb;
   g.ldo = F;
   gemm((p + ".out").c_str(), g);
   if (!dst) return false;
-  if (knob(KNOB_RESIZE_FOLD)) return true;  // vb stays intact until the next block's rcu1 has read it
-  step((p + ".resize").c_str(), [&] { return launch_resize(c.b.vb, dst, B, h, w, F, oh, ow, st); });
+  if (fold_resize) return true;  // vb stays intact until the next block's rcu1 has read it
+  step((p + ".resize").c_str(), [&] { return launch_resize(m.vb, dst, n, h, w, F, dpt_h(r - 2), dpt_w(r - 2), st); });
   return false;
+}
+
+// reassemble i's resize layer: ConvT x4 / ConvT x2 / none / 3x3 stride 2
+void Runner::dpt_resize_layer(DptMaps& m, int n, int i) {
+  const mde_engine& e = *c.e;
+  const int* oc = e.cfg.out_channels;
+  if (i == 0 || i == 1) {
+    const char* wn = i == 0 ? "rs0.w" : "rs1.w";
+    GemmParams g = gemm_convt(m.pj[i], n, e.ph, e.pw, oc[i], w16(wn), ldw(wn), oc[i], i == 0 ? 4 : 2,
+                              i == 0 ? m.l1 : m.l2, i == 0 ? e.c1p : oc[1]);
+    g.bias = w32(i == 0 ? "rs0.b" : "rs1.b");
+    gemm(i == 0 ? "reassemble0.convT4" : "reassemble1.convT2", g);
+  } else if (i == 3) {
+    GemmParams g = conv(m.pj[3], n, e.ph, e.pw, oc[3], "rs3.w", oc[3], 2);
+    g.bias = w32("rs3.b");
+    g.out16 = m.l4;
+    gemm("reassemble3.conv_s2", g);
+  }
+}
+
+void Runner::dpt_layer_rn(DptMaps& m, int n, int i) {
+  const mde_engine& e = *c.e;
+  const int* oc = e.cfg.out_channels;
+  const h16* lay[4] = {m.l1, m.l2, m.pj[2], m.l4};
+  const int cin[4] = {e.c1p, oc[1], oc[2], oc[3]};
+  GemmParams g = conv(lay[i], n, dpt_h(i), dpt_w(i), cin[i], "rn" + std::to_string(i + 1) + ".w", e.F, 1);
+  g.out16 = m.rn[i];
+  gemm(("layer" + std::to_string(i + 1) + "_rn").c_str(), g);
+}
+
+// head.output_conv1 over refinenet1's x2 upsample (fused into the loader)
+void Runner::dpt_head_conv1(DptMaps& m, int n) {
+  const int F = c.e->F, h = dpt_h(0), w = dpt_w(0);
+  GemmParams g = gemm_conv3_up(m.vb, n, h, w, F, 2 * h, 2 * w, w16("head.c1.w"), ldw("head.c1.w"), F / 2);
+  g.bias = w32("head.c1.b");
+  g.out16 = m.c1;
+  g.ldo = F / 2;
+  gemm("head.output_conv1", g);
+}
+
+// head.output_conv2 over the upsample to the input size: 3x3 + ReLU, then the
+// 1x1 conv and the output activation in the epilogue
+void Runner::dpt_head_conv2(DptMaps& m, int n, int metric, float max_depth, const h16* hpe, int hpe_pix, float* out) {
+  const mde_engine& e = *c.e;
+  const int OH = e.cfg.img_h, OW = e.cfg.img_w;  // (ph*14, pw*14)
+  GemmParams g = gemm_conv3_up(m.c1, n, 2 * dpt_h(0), 2 * dpt_w(0), e.F / 2, OH, OW, w16("head.c2.w"),
+                               ldw("head.c2.w"), e.cfg.head_hidden);
+  g.bias = w32("head.c2.b");
+  set_head(g, w32("head.c3.w"), e.head_b2, metric, max_depth, hpe, hpe_pix, out);
+  gemm("head.output_conv2", g);
+}
+
+// One f16 transformer block: norm1 -> qkv -> (after_qkv) -> attention -> proj
+// -> norm2 -> fc1 + GELU -> fc2, the residual stream updated by proj and fc2.
+// Step names are b.name + "norm1" / "qkv" / "attn" / "proj" / "norm2" / "fc1" /
+// "fc2" (tests/golden/layer_schedule.json).
+void Runner::vit_block(const VitBlock& b) {
+  const mde_engine& e = *c.e;
+  const int D = e.D, T = b.T, rows = b.seqs * T, mlp = e.cfg.mlp_hidden;
+  const std::string& p = b.w;
+  auto name = [&](const char* s) { return b.name + s; };
+  // LayerNorm folded across the GEMM boundary (packs with folded weights):
+  // the consumer reads the raw f16 residual rows with W * gamma and the
+  // producers' row partials (GemmParams::lnst_in); otherwise a LayerNorm launch
+  const bool fold = b.st != nullptr;
+  auto normed = [&](const char* norm, const char* ln, const char* lin, int N) {
+    if (fold) {
+      GemmParams g = dense(b.Xh, D, p + lin + ".wf", rows, N, D);
+      set_ln_consumer(g, b.st, w32(p + lin + ".c1"), w32(p + lin + ".c2"), rows, b.eps);
+      return g;
+    }
+    step(name(norm).c_str(), [&] {
+      return launch_layernorm(b.X, b.Hn, w32(p + ln + ".g"), w32(p + ln + ".b"), rows, D, b.eps, T, 0, st, b.Xh);
+    });
+    GemmParams g = dense(b.Hn, D, p + lin + ".w", rows, N, D);
+    g.bias = w32(p + lin + ".b");
+    return g;
+  };
+  {
+    GemmParams g = normed("norm1", "ln1", "qkv", 3 * D);
+    set_qkv(g, b.Q, b.K, b.Vt, T, b.Tpad, e.H, b.qscale);
+    gemm(name("qkv").c_str(), g);
+  }
+  if (b.after_qkv) b.after_qkv();
+  step(name("attn").c_str(),
+       [&] { return launch_attention(b.Q, b.K, b.Vt, b.O, b.seqs, e.H, T, b.Tpad, D, st, b.aws, b.aws_bytes); });
+  {
+    GemmParams g = dense(b.O, D, p + "proj.w", rows, D, D);
+    set_resid(g, w32(p + "proj.b"), w32(p + "ls1"), b.X, b.Xh, D);
+    if (fold) set_ln_producer(g, b.st, rows);
+    gemm(name("proj").c_str(), g);
+  }
+  {
+    GemmParams g = normed("norm2", "ln2", "fc1", mlp);
+    g.emode = E_STORE;
+    g.act = ACT_GELU;
+    g.out16 = b.Mh;
+    g.ldo = mlp;
+    gemm(name("fc1").c_str(), g);
+  }
+  {
+    GemmParams g = dense(b.Mh, mlp, p + "fc2.w", rows, D, mlp);
+    set_resid(g, w32(p + "fc2.b"), w32(p + "ls2"), b.X, b.Xh, D);
+    // small batch: fc2's 64^2 tiles do not fill the chip and each walks a
+    // K = 4D loop -- split K (B = 1: ViT-S 132 tiles x 4, ViT-L 352 x 2;
+    // ViT-L fc2 1.23 -> 0.88 ms per forward; proj at K = 1024 gained
+    // nothing); switch "splitk" = 0 turns it off (A/B, tests)
+    const long long t64 = (long long)((rows + 63) / 64) * ((D + 63) / 64);
+    if (b.ws && (size_t)rows <= b.ws_rows && t64 < 512 && mlp >= 1024 && knob(KNOB_SPLITK))
+      set_resid_splitk(g, b.ws, t64 < 256 ? 4 : 2, fc2_ws_floats(rows, D), b.counters, kTileCnt);
+    if (fold) set_ln_producer(g, b.st, rows);
+    gemm(name("fc2").c_str(), g);
+  }
 }
 
 // The exact-fp32 DPT head (precision "fp32" packs with fp32 head weights):
@@ -412,7 +544,7 @@ void Runner::dav2_head32(int B, float* out) {
 hipError_t Runner::forward_dav2(int B, const void* img, float* out) {
   mde_engine& e = *c.e;
   const PackConfig& cf = e.cfg;
-  const int D = e.D, T = e.T, np = e.np, F = e.F;
+  const int D = e.D, T = e.T, np = e.np;
   const int* oc = cf.out_channels;
   DAV2Buf& b = c.b;
 
@@ -438,82 +570,29 @@ hipError_t Runner::forward_dav2(int B, const void* img, float* out) {
     g.T = T;
     g.pos = w32("pos.patch");
     g.npatch = np;
-    if (fold) {
-      g.lnst_out = b.st;
-      g.lnst_ns = D / 32;
-      g.lnst_rows = B * T;
-    }
+    if (fold) set_ln_producer(g, b.st, B * T);
     gemm("patch_embed", g);
   }
   }  // !enc_f32
-  // ---- DPT head: reassemble (project, resize layer) + layerN_rn of tap i ----
-  const int hs[4] = {4 * e.ph, 2 * e.ph, e.ph, e.h4};
-  const int ws[4] = {4 * e.pw, 2 * e.pw, e.pw, e.w4};
-  const h16* lay[4] = {b.l1, b.l2, b.pj[2], b.l4};
-  const int cin[4] = {e.c1p, oc[1], oc[2], oc[3]};
   char nm[64];
   // the taps' final LayerNorm folded into the projects (packs with proj*.wf):
   // each project runs right after its tap block, on the raw f16 residual rows
   // (cls rows skipped by the GEMM's row map) and that block's LN partials --
   // before the next block rewrites both -- with W * gamma, as qkv / fc1 do
   const bool fold_taps = fold && e.get("proj0.wf") != nullptr;
-  auto project_folded = [&](int i) {
+  auto project = [&](int i) {
     const std::string pn = "proj" + std::to_string(i);
-    GemmParams g = dense(b.Xh, D, pn + ".wf", B * np, oc[i], D);
+    GemmParams g = dense(fold_taps ? b.Xh : b.tap[i], D, pn + (fold_taps ? ".wf" : ".w"), B * np, oc[i], D);
     g.emode = E_STORE;
-    g.bias = w32(pn + ".c2");
-    g.out16 = b.pj[i];
+    g.out16 = b.m.pj[i];
     g.ldo = oc[i];
-    g.lnst_in = b.st;
-    g.lnc1 = w32(pn + ".c1");
-    g.lnst_ns = D / 32;
-    g.lnst_rows = B * T;
-    g.ln_eps = cf.ln_eps;
-    g.a_tok = T;
+    if (fold_taps) {
+      set_ln_consumer(g, b.st, w32(pn + ".c1"), w32(pn + ".c2"), B * T, cf.ln_eps);
+      g.a_tok = T;
+    } else {
+      g.bias = w32(pn + ".b");
+    }
     snprintf(nm, sizeof nm, "reassemble%d.project", i);
-    gemm(nm, g);
-  };
-  auto reassemble = [&](int i) {
-    if (!fold_taps) {
-      GemmParams g = dense(b.tap[i], D, "proj" + std::to_string(i) + ".w", B * np, oc[i], D);
-      g.emode = E_STORE;
-      g.bias = w32("proj" + std::to_string(i) + ".b");
-      g.out16 = b.pj[i];
-      g.ldo = oc[i];
-      snprintf(nm, sizeof nm, "reassemble%d.project", i);
-      gemm(nm, g);
-    }
-    if (i == 0) {
-      GemmParams g = dense(b.pj[0], oc[0], "rs0.w", B * np, 16 * oc[0], oc[0]);
-      g.emode = E_CONVT;
-      g.bias = w32("rs0.b");
-      g.out16 = b.l1;
-      g.s = 4;
-      g.cout = oc[0];
-      g.ldo = e.c1p;
-      g.ih = e.ph;
-      g.iw = e.pw;
-      gemm("reassemble0.convT4", g);
-    } else if (i == 1) {
-      GemmParams g = dense(b.pj[1], oc[1], "rs1.w", B * np, 4 * oc[1], oc[1]);
-      g.emode = E_CONVT;
-      g.bias = w32("rs1.b");
-      g.out16 = b.l2;
-      g.s = 2;
-      g.cout = oc[1];
-      g.ldo = oc[1];
-      g.ih = e.ph;
-      g.iw = e.pw;
-      gemm("reassemble1.convT2", g);
-    } else if (i == 3) {
-      GemmParams g = conv(b.pj[3], B, e.ph, e.pw, oc[3], "rs3.w", oc[3], 2);
-      g.bias = w32("rs3.b");
-      g.out16 = b.l4;
-      gemm("reassemble3.conv_s2", g);
-    }
-    GemmParams g = conv(lay[i], B, hs[i], ws[i], cin[i], "rn" + std::to_string(i + 1) + ".w", F, 1);
-    g.out16 = b.rn[i];
-    snprintf(nm, sizeof nm, "layer%d_rn", i + 1);
     gemm(nm, g);
   };
   int tap = 0;
@@ -553,7 +632,7 @@ hipError_t Runner::forward_dav2(int B, const void* img, float* out) {
         g.T = T;
         g.Tpad = e.Tpad;
         g.heads = e.H;
-        g.qscale = 0.125f * 1.4426950408889634f;  // dh^-0.5 * log2(e): scores in log2 units
+        g.qscale = kQScale;
         snprintf(nm, sizeof nm, "block%d.qkv", i);
         gemm32(nm, g);
       }
@@ -606,190 +685,63 @@ hipError_t Runner::forward_dav2(int B, const void* img, float* out) {
       }
     }
   } else {
-  for (int i = 0; i < cf.depth; ++i) {
-    const std::string p = "b" + std::to_string(i) + ".";
-    const std::string pn = "b" + std::to_string(i + 1) + ".";
-    // small batch: fc2's 64^2 tiles do not fill the chip and each walks a
-    // K = 4D loop -- split K (B = 1: ViT-S 132 tiles x 4, ViT-L 352 x 2;
-    // ViT-L fc2 1.23 -> 0.88 ms per forward; proj at K = 1024 gained
-    // nothing); switch "splitk" = 0 turns it off (A/B, tests)
-    auto split_k = [&](GemmParams& g, int K) {
-      const long long t64 = (long long)((B * T + 63) / 64) * ((D + 63) / 64);
-      if (b.ws && t64 < 512 && K >= 1024 && knob(KNOB_SPLITK)) {
-        g.partial = b.ws;
-        g.splitk = t64 < 256 ? 4 : 2;
-        g.slot_cap = fc2_ws_floats((size_t)B * T, D);
-        g.tile_cnt = split_counters(b.sws);
-        g.tile_cnt_cap = kTileCnt;
+    VitBlock blk;
+    blk.seqs = B;
+    blk.T = T;
+    blk.Tpad = e.Tpad;
+    blk.eps = cf.ln_eps;
+    blk.X = b.X;
+    blk.Xh = b.Xh;
+    blk.Hn = b.Hn;
+    blk.Q = b.Q;
+    blk.K = b.K;
+    blk.Vt = b.Vt;
+    blk.O = b.O;
+    blk.Mh = b.Mh;
+    blk.st = b.st;
+    blk.aws = b.aws;
+    blk.aws_bytes = b.aws_bytes;
+    blk.ws = b.ws;
+    blk.ws_rows = (size_t)c.max_batch * T;  // the context's ws, when it has one, holds its max batch
+    blk.counters = split_counters(b.sws);
+    for (int i = 0; i < cf.depth; ++i) {
+      blk.w = "b" + std::to_string(i) + ".";
+      blk.name = "block" + std::to_string(i) + ".";
+      vit_block(blk);
+      if (tap < 4 && cf.taps[tap] == i) {
+        if (fold_taps) {
+          project(tap);
+        } else {
+          snprintf(nm, sizeof nm, "tap%d.norm", tap);
+          h16* dst = b.tap[tap];
+          step(nm, [&] {
+            return launch_layernorm(b.X, dst, w32("norm.g"), w32("norm.b"), B * T, D, cf.ln_eps, T, 1, st, b.Xh);
+          });
+        }
+        ++tap;
       }
-    };
-    // LayerNorm folded across the GEMM boundary (packs with folded weights):
-    // the consumer reads the raw f16 residual rows with W * gamma and the
-    // producers' row partials (GemmParams::lnst_in); otherwise a LayerNorm launch
-    auto ln_fold = [&](GemmParams& g, const std::string& w) {
-      g.A = b.Xh;
-      g.lda = D;
-      g.W = w16(p + w + ".wf");
-      g.ldw = ldw(p + w + ".wf");
-      g.bias = w32(p + w + ".c2");
-      g.lnst_in = b.st;
-      g.lnc1 = w32(p + w + ".c1");
-      g.lnst_ns = D / 32;
-      g.lnst_rows = B * T;
-      g.ln_eps = cf.ln_eps;
-    };
-    if (!fold) {
-      snprintf(nm, sizeof nm, "block%d.norm1", i);
-      step(nm, [&] {
-        return launch_layernorm(b.X, b.Hn, w32(p + "ln1.g"), w32(p + "ln1.b"), B * T, D, cf.ln_eps, T, 0, st, b.Xh);
-      });
     }
-    {
-      GemmParams g = dense(b.Hn, D, p + "qkv.w", B * T, 3 * D, D);
-      g.emode = E_QKV;
-      g.bias = w32(p + "qkv.b");
-      g.q = b.Q;
-      g.k = b.K;
-      g.vt = b.Vt;
-      g.T = T;
-      g.Tpad = e.Tpad;
-      g.heads = e.H;
-      g.qscale = 0.125f * 1.4426950408889634f;  // dh^-0.5 * log2(e): scores in log2 units
-      if (fold) ln_fold(g, "qkv");
-      snprintf(nm, sizeof nm, "block%d.qkv", i);
-      gemm(nm, g);
-    }
-    snprintf(nm, sizeof nm, "block%d.attn", i);
-    step(nm, [&] { return launch_attention(b.Q, b.K, b.Vt, b.O, B, e.H, T, e.Tpad, D, st, b.aws, b.aws_bytes); });
-    {
-      GemmParams g = dense(b.O, D, p + "proj.w", B * T, D, D);
-      g.emode = E_RESID;
-      g.bias = w32(p + "proj.b");
-      g.ls = w32(p + "ls1");
-      g.x32 = b.X;
-      g.xh = b.Xh;
-      g.ldo = D;
-      if (fold) {
-        g.lnst_out = b.st;
-        g.lnst_ns = D / 32;
-        g.lnst_rows = B * T;
-      }
-      snprintf(nm, sizeof nm, "block%d.proj", i);
-      gemm(nm, g);
-    }
-    if (!fold) {
-      snprintf(nm, sizeof nm, "block%d.norm2", i);
-      step(nm, [&] {
-        return launch_layernorm(b.X, b.Hn, w32(p + "ln2.g"), w32(p + "ln2.b"), B * T, D, cf.ln_eps, T, 0, st, b.Xh);
-      });
-    }
-    {
-      GemmParams g = dense(b.Hn, D, p + "fc1.w", B * T, cf.mlp_hidden, D);
-      g.emode = E_STORE;
-      g.bias = w32(p + "fc1.b");
-      g.act = ACT_GELU;
-      g.out16 = b.Mh;
-      g.ldo = cf.mlp_hidden;
-      if (fold) ln_fold(g, "fc1");
-      snprintf(nm, sizeof nm, "block%d.fc1", i);
-      gemm(nm, g);
-    }
-    {
-      GemmParams g = dense(b.Mh, cf.mlp_hidden, p + "fc2.w", B * T, D, cf.mlp_hidden);
-      g.emode = E_RESID;
-      g.bias = w32(p + "fc2.b");
-      g.ls = w32(p + "ls2");
-      g.x32 = b.X;
-      g.xh = b.Xh;
-      g.ldo = D;
-      split_k(g, cf.mlp_hidden);
-      if (fold) {
-        g.lnst_out = b.st;
-        g.lnst_ns = D / 32;
-        g.lnst_rows = B * T;
-      }
-      snprintf(nm, sizeof nm, "block%d.fc2", i);
-      gemm(nm, g);
-    }
-    if (tap < 4 && cf.taps[tap] == i) {
-      if (fold_taps) {
-        project_folded(tap);
-      } else {
-        snprintf(nm, sizeof nm, "tap%d.norm", tap);
-        h16* dst = b.tap[tap];
-        step(nm, [&] {
-          return launch_layernorm(b.X, dst, w32("norm.g"), w32("norm.b"), B * T, D, cf.ln_eps, T, 1, st, b.Xh);
-        });
-      }
-      ++tap;
-    }
-  }
   }  // f16 encoder
   if (tap != 4) return hipErrorInvalidValue;
   if (e.head_f32) {
     dav2_head32(B, out);
     return err;
   }
-  for (int i = 0; i < 4; ++i) reassemble(i);
+  // ---- DPT head: reassemble (project, resize layer) + layerN_rn of tap i ----
+  for (int i = 0; i < 4; ++i) {
+    if (!fold_taps) project(i);
+    dpt_resize_layer(b.m, B, i);
+    dpt_layer_rn(b.m, B, i);
+  }
   // ---- fusion (refinenet4 .. refinenet1) ----
-  bool up = dav2_fusion(4, b.rn[3], nullptr, B, hs[3], ws[3], b.p4, hs[2], ws[2]);
-  up = dav2_fusion(3, b.p4, b.rn[2], B, hs[2], ws[2], b.p3, hs[1], ws[1], up ? b.vb : nullptr, hs[3], ws[3]);
-  up = dav2_fusion(2, b.p3, b.rn[1], B, hs[1], ws[1], b.p2, hs[0], ws[0], up ? b.vb : nullptr, hs[2], ws[2]);
-  dav2_fusion(1, b.p2, b.rn[0], B, hs[0], ws[0], nullptr, 0, 0, up ? b.vb : nullptr, hs[1], ws[1]);  // 1x1 result in vb at hs[0] x ws[0]
+  const bool rf = knob(KNOB_RESIZE_FOLD) != 0;
+  bool up = dpt_fusion(b.m, B, 4, false, rf);
+  up = dpt_fusion(b.m, B, 3, false, rf, up ? b.m.vb : nullptr, dpt_h(3), dpt_w(3));
+  up = dpt_fusion(b.m, B, 2, false, rf, up ? b.m.vb : nullptr, dpt_h(2), dpt_w(2));
+  dpt_fusion(b.m, B, 1, false, rf, up ? b.m.vb : nullptr, dpt_h(1), dpt_w(1));  // 1x1 result in vb at level 0's size
   // ---- head ----
-  const int H1 = 2 * hs[0], W1 = 2 * ws[0];  // refinenet1 upsample x2 (fused into output_conv1's loader)
-  {
-    GemmParams g;
-    g.amode = A_CONV3_UP;
-    g.emode = E_STORE;
-    g.A = b.vb;
-    g.cb = B;
-    g.ch = hs[0];
-    g.cw = ws[0];
-    g.cc = F;
-    g.uh = H1;
-    g.uw = W1;
-    g.oh = H1;
-    g.ow = W1;
-    g.stride = 1;
-    g.W = w16("head.c1.w");
-    g.ldw = ldw("head.c1.w");
-    g.M = B * H1 * W1;
-    g.N = F / 2;
-    g.K = 9 * F;
-    g.bias = w32("head.c1.b");
-    g.out16 = b.c1;
-    g.ldo = F / 2;
-    gemm("head.output_conv1", g);
-  }
-  {
-    const int OH = cf.img_h, OW = cf.img_w;  // (ph*14, pw*14)
-    GemmParams g;
-    g.amode = A_CONV3_UP;
-    g.emode = E_HEAD;
-    g.A = b.c1;
-    g.cb = B;
-    g.ch = H1;
-    g.cw = W1;
-    g.cc = F / 2;
-    g.uh = OH;
-    g.uw = OW;
-    g.oh = OH;
-    g.ow = OW;
-    g.stride = 1;
-    g.W = w16("head.c2.w");
-    g.ldw = ldw("head.c2.w");
-    g.M = B * OH * OW;
-    g.N = cf.head_hidden;
-    g.K = 9 * (F / 2);
-    g.bias = w32("head.c2.b");
-    g.w2 = w32("head.c3.w");
-    g.b2 = e.head_b2;
-    g.head_metric = cf.metric;
-    g.max_depth = cf.max_depth;
-    g.out32 = out;
-    gemm("head.output_conv2", g);
-  }
+  dpt_head_conv1(b.m, B);
+  dpt_head_conv2(b.m, B, cf.metric, cf.max_depth, nullptr, 0, out);
   return err;
 }
 
@@ -1291,845 +1243,6 @@ int mde_rt_event_elapsed_ms(float* ms, void* a, void* b) {
   if (!ms) return fail(MDE_ERR_ARG, "null argument");
   HIP_OR(hipEventElapsedTime(ms, (hipEvent_t)a, (hipEvent_t)b), "hipEventElapsedTime");
   return MDE_OK;
-}
-
-// ---- kernel-level entry points ------------------------------------------------
-#define OP_RET(call, what)                                   \
-  do {                                                       \
-    hipError_t e_ = (call);                                  \
-    if (e_ == hipErrorInvalidValue) return fail(MDE_ERR_ARG, what ": invalid shape/argument"); \
-    if (e_ != hipSuccess) return hip_fail(e_, what);          \
-    return MDE_OK;                                           \
-  } while (0)
-
-int mde_op_patch_prep_u8(const unsigned char* img, int batch, int h, int w, float scale, const float* mean3,
-                         const float* std3, void* patches, void* st) {
-  if (!img || !mean3 || !std3 || !patches || batch < 1 || h % 14 || w % 14 || h < 14 || w < 14)
-    return fail(MDE_ERR_ARG, "mde_op_patch_prep_u8: bad argument (h, w multiples of 14)");
-  OP_RET(launch_patch_prep_u8(img, (h16*)patches, nullptr, nullptr, batch, h, w, h / 14, w / 14, 1, 0, scale, mean3,
-                              std3, (hipStream_t)st),
-         "patch_prep_u8");
-}
-
-int mde_op_depth_postprocess(const float* depth, int batch, int ih, int iw, float* out, int oh, int ow, float lo,
-                             float hi, void* st) {
-  if (!depth || !out || batch < 1 || ih < 1 || iw < 1 || oh < 1 || ow < 1)
-    return fail(MDE_ERR_ARG, "mde_op_depth_postprocess: bad argument");
-  OP_RET(launch_depth_postprocess(depth, batch, ih, iw, out, oh, ow, lo, hi, (hipStream_t)st), "depth_postprocess");
-}
-
-namespace {
-const char* resize_u8_arg_error(const void* src, const void* dst, int batch, int sh, int sw, int pitch, int oh,
-                                int ow) {
-  if (!src || !dst) return "null pointer";
-  if (batch < 1 || sh < 1 || sw < 1 || oh < 1 || ow < 1) return "batch and sizes must be positive";
-  if (pitch < 3 * (long long)sw) return "pitch < 3 * sw";
-  return nullptr;
-}
-}  // namespace
-
-int mde_op_resize_u8(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
-                     unsigned char* dst_u8, int oh, int ow, void* st) {
-  if (const char* why = resize_u8_arg_error(src, dst_u8, batch, sh, sw, pitch, oh, ow))
-    return fail(MDE_ERR_ARG, std::string("mde_op_resize_u8: ") + why);
-  OP_RET(launch_resize_u8(src, batch, sh, sw, pitch, swap_rb, nullptr, dst_u8, oh, ow, (hipStream_t)st),
-         "mde_op_resize_u8");
-}
-
-int mde_op_resize_u8_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
-                          const float* lut3x256, float* dst_f32_nchw, int oh, int ow, void* st) {
-  const char* why = resize_u8_arg_error(src, dst_f32_nchw, batch, sh, sw, pitch, oh, ow);
-  if (!why && !lut3x256) why = "null pointer";
-  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_resize_u8_norm: ") + why);
-  OP_RET(launch_resize_u8(src, batch, sh, sw, pitch, swap_rb, lut3x256, dst_f32_nchw, oh, ow, (hipStream_t)st),
-         "mde_op_resize_u8_norm");
-}
-
-namespace {
-// the Depth Pro photo ops index a plane with an int and put the batch on grid.y
-const char* dp_photo_geometry_error(int batch, int sh, int sw, int oh, int ow) {
-  if (batch < 1 || sh < 1 || sw < 1 || oh < 1 || ow < 1) return "batch and sizes must be positive";
-  const long long lim = 0x7fffffffLL - 256;
-  if ((long long)sh * sw >= lim || (long long)oh * ow >= lim) return "a plane of 2^31 - 256 elements or more";
-  if (batch > 65535) return "batch > 65535";
-  return nullptr;
-}
-}  // namespace
-
-int mde_op_dp_preprocess(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
-                         const float* lut256, float* dst_f32_nchw, int oh, int ow, void* st) {
-  const char* why = dp_photo_geometry_error(batch, sh, sw, oh, ow);
-  if (!src || !lut256 || !dst_f32_nchw) why = "null pointer";
-  if (!why && pitch < 3 * (long long)sw) why = "pitch < 3 * sw";
-  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_dp_preprocess: ") + why);
-  OP_RET(launch_dp_preprocess(src, batch, sh, sw, pitch, swap_rb, lut256, dst_f32_nchw, oh, ow, (hipStream_t)st),
-         "mde_op_dp_preprocess");
-}
-
-int mde_op_dp_postprocess(const float* inv, int batch, int ih, int iw, const float* fov_deg, float f_px,
-                          float* f_px_out, float* depth, int oh, int ow, void* st) {
-  const char* why = (!inv || !depth) ? "null pointer" : dp_photo_geometry_error(batch, ih, iw, oh, ow);
-  if (!why && !fov_deg && !(f_px > 0.f)) why = "fov_deg is null and f_px <= 0";
-  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_dp_postprocess: ") + why);
-  OP_RET(launch_dp_postprocess(inv, batch, ih, iw, fov_deg, f_px, f_px_out, depth, oh, ow, (hipStream_t)st),
-         "mde_op_dp_postprocess");
-}
-
-int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
-  if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
-  DpPyramid pyr;
-  pyr.nlev = 3;
-  const int f[3] = {1, 2, 4}, n[3] = {5, 3, 1}, stride[3] = {288, 192, 384};
-  int first = 0;
-  for (int i = 0; i < 3; ++i) {
-    pyr.first[i] = first;
-    pyr.n[i] = n[i];
-    pyr.stride[i] = stride[i];
-    pyr.f[i] = f[i];
-    first += n[i] * n[i];
-  }
-  pyr.nseq = first;
-  OP_RET(launch_dp_patch_prep(img, (h16*)patches, batch, size, 24, pyr, (hipStream_t)st), "dp_pyramid_patches");
-}
-
-int mde_op_merge_tokens(const float* x32, int batch, int tokens, int dim, int n, int g, int pad, int base,
-                        const float* gamma, const float* beta, float eps, void* out, void* st) {
-  if (!x32 || !out || batch < 1 || (gamma == nullptr) != (beta == nullptr))
-    return fail(MDE_ERR_ARG, "mde_op_merge_tokens: bad argument");
-  DpMerge m;
-  m.B = batch;
-  m.n = n;
-  m.G = g;
-  m.pad = pad;
-  m.base = base;
-  m.T = tokens;
-  OP_RET(launch_merge_tokens(x32, (h16*)out, gamma, beta, dim, m, eps, (hipStream_t)st), "merge_tokens");
-}
-
-int mde_op_qk_norm_rope(void* q, void* k, const float* qg, const float* qb, const float* kg, const float* kb, int bh,
-                        int tokens, int tokens_pad, int frame_tokens, int npre, int grid_w, const float* rope_cos,
-                        const float* rope_sin, float q_scale, float eps, void* st) {
-  if (!q || !k || !qg || !qb || !kg || !kb || !rope_cos || !rope_sin) return fail(MDE_ERR_ARG, "null argument");
-  RopeGeom geo;
-  geo.T = tokens;
-  geo.Tpad = tokens_pad;
-  geo.P = frame_tokens;
-  geo.npre = npre;
-  geo.gw = grid_w;
-  geo.qscale = q_scale;
-  geo.eps = eps;
-  OP_RET(launch_qk_norm_rope((h16*)q, (h16*)k, qg, qb, kg, kb, rope_cos, rope_sin, bh, geo, (hipStream_t)st),
-         "qk_norm_rope");
-}
-
-int mde_op_tap_concat_ln(const float* xa, const float* xb, int nseq, int tokens, int npre, int dim, const float* g,
-                         const float* b, float eps, void* out, void* st) {
-  if (!xa || !xb || !g || !b || !out || nseq < 0) return fail(MDE_ERR_ARG, "null argument");
-  OP_RET(launch_tap_concat_ln(xa, xb, (h16*)out, g, b, nseq, tokens, npre, dim, eps, (hipStream_t)st),
-         "tap_concat_ln");
-}
-
-int mde_op_layernorm_f16(const void* x, void* y, const float* g, const float* b, int rows, int dim, float eps,
-                         int tokens, int skip_cls, void* st) {
-  if (!x || !y || !g || !b) return fail(MDE_ERR_ARG, "null argument");
-  if (skip_cls && tokens < 2) return fail(MDE_ERR_ARG, "skip_cls needs tokens >= 2");
-  OP_RET(launch_layernorm(nullptr, (h16*)y, g, b, rows, dim, eps, tokens > 0 ? tokens : 1, skip_cls, (hipStream_t)st,
-                          (const h16*)x),
-         "layernorm_f16");
-}
-
-int mde_op_layernorm(const float* x, void* y, const float* g, const float* b, int rows, int dim, float eps,
-                     int tokens, int skip_cls, void* st) {
-  if (!x || !y || !g || !b) return fail(MDE_ERR_ARG, "null argument");
-  if (skip_cls && tokens < 2) return fail(MDE_ERR_ARG, "skip_cls needs tokens >= 2");
-  OP_RET(launch_layernorm(x, (h16*)y, g, b, rows, dim, eps, tokens > 0 ? tokens : 1, skip_cls, (hipStream_t)st),
-         "layernorm");
-}
-
-int mde_op_linear(const void* a, int lda, const void* w, int ldw, int m, int n, int k, const float* bias, int act,
-                  void* out, int ldo, void* st) {
-  if (!a || !w || !out) return fail(MDE_ERR_ARG, "null argument");
-  GemmParams g;
-  g.A = (const h16*)a;
-  g.lda = lda;
-  g.W = (const h16*)w;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.act = act;
-  g.out16 = (h16*)out;
-  g.ldo = ldo;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear");
-}
-
-int mde_op_linear_residual(const void* a, int lda, const void* w, int ldw, int m, int n, int k, const float* bias,
-                           const float* ls, float* x32, int ldx, void* st) {
-  if (!a || !w || !bias || !ls || !x32) return fail(MDE_ERR_ARG, "null argument");
-  GemmParams g;
-  g.emode = E_RESID;
-  g.A = (const h16*)a;
-  g.lda = lda;
-  g.W = (const h16*)w;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.ls = ls;
-  g.x32 = x32;
-  g.ldo = ldx;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual");
-}
-
-// E_QKV geometry: V^T stores key t at vt_pos(t), which swaps bits 2 and 3 of
-// t, so a row of tokens_pad keys holds whole 16-key groups only when
-// tokens_pad % 16 == 0 (otherwise the last group's keys land in the next row)
-static const char* qkv_geometry_error(int batch, int tokens, int heads, int tokens_pad) {
-  if (batch <= 0 || tokens <= 0 || heads <= 0) return "batch, tokens and heads must be > 0";
-  if (tokens_pad < tokens) return "tokens_pad < tokens";
-  if (tokens_pad % 16) return "tokens_pad % 16 != 0 (V^T key permutation works on 16-key groups)";
-  return nullptr;
-}
-
-int mde_op_qkv(const void* a, const void* w, int ldw, const float* bias, int batch, int tokens, int heads,
-               int tokens_pad, float qscale, void* q, void* k, void* vt, void* st) {
-  if (!a || !w || !bias || !q || !k || !vt) return fail(MDE_ERR_ARG, "null argument");
-  if (const char* why = qkv_geometry_error(batch, tokens, heads, tokens_pad)) return fail(MDE_ERR_ARG, why);
-  GemmParams g;
-  g.emode = E_QKV;
-  const int D = heads * 64;
-  g.A = (const h16*)a;
-  g.lda = D;
-  g.W = (const h16*)w;
-  g.ldw = ldw;
-  g.M = batch * tokens;
-  g.N = 3 * D;
-  g.K = D;
-  g.bias = bias;
-  g.q = (h16*)q;
-  g.k = (h16*)k;
-  g.vt = (h16*)vt;
-  g.T = tokens;
-  g.Tpad = tokens_pad;
-  g.heads = heads;
-  g.qscale = qscale;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "qkv");
-}
-
-int mde_op_linear_residual_f16(const void* a, int lda, const void* w, int ldw, int m, int n, int k, const float* bias,
-                               const float* ls, void* xh, int ldx, float* ln_partials, void* st) {
-  if (!a || !w || !bias || !ls || !xh) return fail(MDE_ERR_ARG, "null argument");
-  if (ln_partials && (n & 31)) return fail(MDE_ERR_ARG, "ln_partials need n % 32 == 0");
-  GemmParams g;
-  g.emode = E_RESID;
-  g.A = (const h16*)a;
-  g.lda = lda;
-  g.W = (const h16*)w;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.ls = ls;
-  g.xh = (h16*)xh;
-  g.ldo = ldx;
-  g.lnst_out = ln_partials;
-  g.lnst_ns = n / 32;
-  g.lnst_rows = m;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual_f16");
-}
-
-int mde_op_linear_lnfold(const void* x, const float* ln_partials, float eps, const void* wg, int ldw, const float* c1,
-                         const float* c2, int m, int n, int k, int act, void* out, int ldo, void* st) {
-  if (!x || !ln_partials || !wg || !c1 || !c2 || !out) return fail(MDE_ERR_ARG, "null argument");
-  if (k & 31) return fail(MDE_ERR_ARG, "k % 32 != 0");
-  GemmParams g;
-  g.A = (const h16*)x;
-  g.lda = k;
-  g.W = (const h16*)wg;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = c2;
-  g.act = act;
-  g.out16 = (h16*)out;
-  g.ldo = ldo;
-  g.lnst_in = ln_partials;
-  g.lnc1 = c1;
-  g.lnst_ns = k / 32;
-  g.lnst_rows = m;
-  g.ln_eps = eps;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_lnfold");
-}
-
-int mde_op_qkv_lnfold(const void* x, const float* ln_partials, float eps, const void* wg, int ldw, const float* c1,
-                      const float* c2, int batch, int tokens, int heads, int tokens_pad, float qscale, void* q, void* k,
-                      void* vt, void* st) {
-  if (!x || !ln_partials || !wg || !c1 || !c2 || !q || !k || !vt) return fail(MDE_ERR_ARG, "null argument");
-  if (const char* why = qkv_geometry_error(batch, tokens, heads, tokens_pad)) return fail(MDE_ERR_ARG, why);
-  GemmParams g;
-  g.emode = E_QKV;
-  const int D = heads * 64;
-  g.A = (const h16*)x;
-  g.lda = D;
-  g.W = (const h16*)wg;
-  g.ldw = ldw;
-  g.M = batch * tokens;
-  g.N = 3 * D;
-  g.K = D;
-  g.bias = c2;
-  g.q = (h16*)q;
-  g.k = (h16*)k;
-  g.vt = (h16*)vt;
-  g.T = tokens;
-  g.Tpad = tokens_pad;
-  g.heads = heads;
-  g.qscale = qscale;
-  g.lnst_in = ln_partials;
-  g.lnc1 = c1;
-  g.lnst_ns = D / 32;
-  g.lnst_rows = g.M;
-  g.ln_eps = eps;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "qkv_lnfold");
-}
-
-int mde_op_attention(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int tokens,
-                     int tokens_pad, int ldo, void* st) {
-  if (!q || !k || !vt || !o) return fail(MDE_ERR_ARG, "null argument");
-  OP_RET(launch_attention((const h16*)q, (const h16*)k, (const h16*)vt, (h16*)o, batch, heads, tokens, tokens_pad,
-                          ldo, (hipStream_t)st),
-         "attention");
-}
-
-int mde_op_attention_ws(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int tokens,
-                        int tokens_pad, int ldo, void* ws, size_t ws_bytes, void* st) {
-  if (!q || !k || !vt || !o || (!ws && ws_bytes)) return fail(MDE_ERR_ARG, "null argument");
-  OP_RET(launch_attention((const h16*)q, (const h16*)k, (const h16*)vt, (h16*)o, batch, heads, tokens, tokens_pad,
-                          ldo, (hipStream_t)st, (float*)ws, ws_bytes),
-         "attention_ws");
-}
-
-int mde_op_attention_cfg(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int tokens,
-                         int tokens_pad, int ldo, const char* cfg, void* ws, size_t ws_bytes, void* st) {
-  if (!q || !k || !vt || !o || (!ws && ws_bytes)) return fail(MDE_ERR_ARG, "null argument");
-  OP_RET(launch_attention((const h16*)q, (const h16*)k, (const h16*)vt, (h16*)o, batch, heads, tokens, tokens_pad,
-                          ldo, (hipStream_t)st, (float*)ws, ws_bytes, cfg),
-         "attention_cfg");
-}
-
-size_t mde_op_attention_ws_bytes(int batch, int heads, int tokens) {
-  return batch > 0 && heads > 0 && tokens > 0 ? attention_split_ws_bytes(batch, heads, tokens) : 0;
-}
-
-int mde_op_linear32(const float* a, int lda, const float* w, int ldw, int m, int n, int k, const float* bias, int act,
-                    float* out, int ldo, void* st) {
-  if (!a || !w || !out) return fail(MDE_ERR_ARG, "null argument");
-  Gemm32Params g;
-  g.A = a;
-  g.lda = lda;
-  g.W = w;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.act = act;
-  g.out32 = out;
-  g.ldo = ldo;
-  OP_RET(launch_gemm32(g, (hipStream_t)st), "linear32");
-}
-
-int mde_op_conv3x3_32(const float* in, int batch, int h, int w, int cin, const float* wt, int ldw, int cout,
-                      int stride, int relu_in, const float* bias, int act, const float* res0, const float* res1,
-                      float* out, void* st) {
-  if (!in || !wt || !out) return fail(MDE_ERR_ARG, "null argument");
-  if (stride != 1 && stride != 2) return fail(MDE_ERR_ARG, "stride must be 1 or 2");
-  if (batch <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return fail(MDE_ERR_ARG, "bad shape");
-  Gemm32Params g;
-  g.amode = A_CONV3;
-  g.emode = E_STORE;
-  g.A = in;
-  g.cb = batch;
-  g.ch = h;
-  g.cw = w;
-  g.cc = cin;
-  g.stride = stride;
-  g.oh = (h - 1) / stride + 1;
-  g.ow = (w - 1) / stride + 1;
-  g.W = wt;
-  g.ldw = ldw;
-  g.M = batch * g.oh * g.ow;
-  g.N = cout;
-  g.K = 9 * cin;
-  g.relu_in = relu_in;
-  g.bias = bias;
-  g.act = act;
-  g.res0 = res0;
-  g.res1 = res1;
-  g.out32 = out;
-  g.ldo = cout;
-  OP_RET(launch_gemm32(g, (hipStream_t)st), "conv3x3_32");
-}
-
-int mde_op_conv_transpose32(const float* in, int batch, int h, int w, int cin, const float* wt, int ldw, int cout,
-                            int stride, const float* bias, float* out, void* st) {
-  if (!in || !wt || !out) return fail(MDE_ERR_ARG, "null argument");
-  if (batch <= 0 || h <= 0 || w <= 0 || stride < 1) return fail(MDE_ERR_ARG, "bad shape");
-  Gemm32Params g;
-  g.emode = E_CONVT;
-  g.A = in;
-  g.lda = cin;
-  g.W = wt;
-  g.ldw = ldw;
-  g.M = batch * h * w;
-  g.N = stride * stride * cout;
-  g.K = cin;
-  g.bias = bias;
-  g.out32 = out;
-  g.ldo = cout;
-  g.s = stride;
-  g.cout = cout;
-  g.cb = batch;
-  g.ih = h;
-  g.iw = w;
-  OP_RET(launch_gemm32(g, (hipStream_t)st), "conv_transpose32");
-}
-
-int mde_op_resize32(const float* in, int batch, int h, int w, int c, int oh, int ow, float* out, void* st) {
-  if (!in || !out) return fail(MDE_ERR_ARG, "null argument");
-  OP_RET(launch_resize32(in, out, batch, h, w, c, oh, ow, (hipStream_t)st), "resize32");
-}
-
-int mde_op_linear_residual32(const float* a, int lda, const float* w, int ldw, int m, int n, int k,
-                             const float* bias, const float* ls, float* x32, int ldx, void* st) {
-  if (!a || !w || !ls || !x32) return fail(MDE_ERR_ARG, "null argument");
-  Gemm32Params g;
-  g.emode = E_RESID;
-  g.A = a;
-  g.lda = lda;
-  g.W = w;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.ls = ls;
-  g.x32 = x32;
-  g.ldo = ldx;
-  OP_RET(launch_gemm32(g, (hipStream_t)st), "linear_residual32");
-}
-
-int mde_op_qkv32(const float* a, const float* w, int ldw, const float* bias, int batch, int tokens, int heads,
-                 int tokens_pad, float q_scale, float* q, float* k, float* v, void* st) {
-  if (!a || !w || !q || !k || !v) return fail(MDE_ERR_ARG, "null argument");
-  Gemm32Params g;
-  g.emode = E_QKV;
-  g.A = a;
-  g.lda = heads * 64;
-  g.W = w;
-  g.ldw = ldw;
-  g.M = batch * tokens;
-  g.N = 3 * heads * 64;
-  g.K = heads * 64;
-  g.bias = bias;
-  g.q = q;
-  g.k = k;
-  g.v = v;
-  g.T = tokens;
-  g.Tpad = tokens_pad;
-  g.heads = heads;
-  g.qscale = q_scale;
-  OP_RET(launch_gemm32(g, (hipStream_t)st), "qkv32");
-}
-
-int mde_op_attention32(const float* q, const float* k, const float* v, float* o, int batch, int heads, int tokens,
-                       int tokens_pad, int ldo, void* st) {
-  if (!q || !k || !v || !o) return fail(MDE_ERR_ARG, "null argument");
-  OP_RET(launch_attention32(q, k, v, o, batch, heads, tokens, tokens_pad, ldo, (hipStream_t)st), "attention32");
-}
-
-int mde_op_patch_embed(const float* img, int batch, int h, int w, const void* wt, int ldw, const float* bias,
-                       const float* pos_patch, const float* cls_pos, int dim, void* scratch, float* x32, void* st) {
-  if (!img || !wt || !bias || !pos_patch || !cls_pos || !scratch || !x32) return fail(MDE_ERR_ARG, "null argument");
-  if (h % 14 || w % 14) return fail(MDE_ERR_ARG, "image size must be a multiple of 14");
-  const int ph = h / 14, pw = w / 14, T = ph * pw + 1;
-  hipError_t e = launch_patch_prep(img, (h16*)scratch, x32, cls_pos, batch, h, w, ph, pw, T, dim, (hipStream_t)st);
-  if (e != hipSuccess) return hip_fail(e, "patch_prep");
-  GemmParams g;
-  g.emode = E_PATCH;
-  g.A = (const h16*)scratch;
-  g.lda = 672;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = batch * ph * pw;
-  g.N = dim;
-  g.K = 672;
-  g.bias = bias;
-  g.x32 = x32;
-  g.ldo = dim;
-  g.T = T;
-  g.pos = pos_patch;
-  g.npatch = ph * pw;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "patch_embed");
-}
-
-namespace {
-// GemmParams of a 3x3 / pad-1 conv over an NHWC f16 map (the mde_op_conv3x3* ops)
-GemmParams conv3x3_params(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout,
-                          int stride, int relu_in, const float* bias, int act, const void* res0, const void* res1,
-                          void* out) {
-  GemmParams g;
-  g.amode = A_CONV3;
-  g.A = (const h16*)in;
-  g.cb = batch;
-  g.ch = h;
-  g.cw = w;
-  g.cc = cin;
-  g.stride = stride;
-  g.oh = (h - 1) / stride + 1;
-  g.ow = (w - 1) / stride + 1;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = batch * g.oh * g.ow;
-  g.N = cout;
-  g.K = 9 * cin;
-  g.relu_in = relu_in;
-  g.bias = bias;
-  g.act = act;
-  g.res0 = (const h16*)res0;
-  g.res1 = (const h16*)res1;
-  g.out16 = (h16*)out;
-  g.ldo = cout;
-  return g;
-}
-}  // namespace
-
-int mde_op_conv3x3(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout, int stride,
-                   int relu_in, const float* bias, int act, const void* res0, const void* res1, void* out,
-                   void* st) {
-  if (!in || !wt || !out) return fail(MDE_ERR_ARG, "null argument");
-  if (stride != 1 && stride != 2) return fail(MDE_ERR_ARG, "stride must be 1 or 2");
-  const GemmParams g = conv3x3_params(in, batch, h, w, cin, wt, ldw, cout, stride, relu_in, bias, act, res0, res1, out);
-  OP_RET(launch_gemm(g, (hipStream_t)st), "conv3x3");
-}
-
-int mde_op_conv3x3_ws(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout, int stride,
-                      int relu_in, const float* bias, int act, const void* res0, const void* res1, void* out,
-                      float* ws, size_t ws_floats, int* slices, void* st) {
-  if (!in || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
-  if (stride != 1 && stride != 2) return fail(MDE_ERR_ARG, "stride must be 1 or 2");
-  GemmParams g = conv3x3_params(in, batch, h, w, cin, wt, ldw, cout, stride, relu_in, bias, act, res0, res1, out);
-  g.partial = ws;
-  g.partial_cap = ws_floats;
-  if (slices) *slices = gemm_store_split_slices(g);
-  OP_RET(launch_gemm(g, (hipStream_t)st), "conv3x3_ws");
-}
-
-int mde_op_linear_ws(const void* a, int lda, const void* wt, int ldw, int m, int n, int k, const float* bias, int act,
-                     void* out, int ldo, float* ws, size_t ws_floats, int* slices, void* st) {
-  if (!a || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
-  GemmParams g;
-  g.amode = A_DENSE;
-  g.A = (const h16*)a;
-  g.lda = lda;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.act = act;
-  g.out16 = (h16*)out;
-  g.ldo = ldo;
-  g.partial = ws;
-  g.partial_cap = ws_floats;
-  if (slices) *slices = gemm_store_split_slices(g);
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_ws");
-}
-
-int mde_op_conv3x3_up(const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt, int ldw,
-                      int cout, const float* bias, int act, void* out, void* st) {
-  if (!in || !wt || !out) return fail(MDE_ERR_ARG, "null argument");
-  GemmParams g;
-  g.amode = A_CONV3_UP;
-  g.A = (const h16*)in;
-  g.cb = batch;
-  g.ch = sh;
-  g.cw = sw;
-  g.cc = cin;
-  g.uh = uh;
-  g.uw = uw;
-  g.oh = uh;
-  g.ow = uw;
-  g.stride = 1;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = batch * uh * uw;
-  g.N = cout;
-  g.K = 9 * cin;
-  g.bias = bias;
-  g.act = act;
-  g.out16 = (h16*)out;
-  g.ldo = cout;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "conv3x3_up");
-}
-
-int mde_op_conv_transpose(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout,
-                          int stride, const float* bias, void* out, void* st) {
-  if (!in || !wt || !bias || !out) return fail(MDE_ERR_ARG, "null argument");
-  GemmParams g;
-  g.emode = E_CONVT;
-  g.A = (const h16*)in;
-  g.lda = cin;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = batch * h * w;
-  g.N = stride * stride * cout;
-  g.K = cin;
-  g.bias = bias;
-  g.out16 = (h16*)out;
-  g.s = stride;
-  g.cout = cout;
-  g.ldo = cout;
-  g.ih = h;
-  g.iw = w;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "conv_transpose");
-}
-
-int mde_op_resize_bilinear(const void* in, int batch, int ih, int iw, int c, int oh, int ow, void* out, void* st) {
-  if (!in || !out) return fail(MDE_ERR_ARG, "null argument");
-  OP_RET(launch_resize((const h16*)in, (h16*)out, batch, ih, iw, c, oh, ow, (hipStream_t)st), "resize_bilinear");
-}
-
-int mde_op_depth_head(const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt, int ldw,
-                      const float* bias, const float* w2, float b2, int metric, float max_depth, float* out,
-                      void* st) {
-  if (!in || !wt || !bias || !w2 || !out) return fail(MDE_ERR_ARG, "null argument");
-  GemmParams g;
-  g.amode = A_CONV3_UP;
-  g.emode = E_HEAD;
-  g.A = (const h16*)in;
-  g.cb = batch;
-  g.ch = sh;
-  g.cw = sw;
-  g.cc = cin;
-  g.uh = uh;
-  g.uw = uw;
-  g.oh = uh;
-  g.ow = uw;
-  g.stride = 1;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = batch * uh * uw;
-  g.N = 32;
-  g.K = 9 * cin;
-  g.bias = bias;
-  g.w2 = w2;
-  g.b2 = b2;
-  g.head_metric = metric;
-  g.max_depth = max_depth;
-  g.out32 = out;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "depth_head");
-}
-
-// ---- the GemmParams options only the engine graphs set, one wrapper each ----
-// (no kernel code and no policy here: launch_gemm picks the route as it does
-// for the engines; tests/test_gpu_ops_engine_paths.py)
-namespace {
-// fused split-K operands (GemmParams::tile_cnt): the slots live in ws, and
-// every 64^2 tile of the problem has a counter (the 128^2 grids are smaller)
-const char* fused_split_error(const float* ws, size_t ws_floats, const int* tile_cnt, int tile_cnt_cap,
-                              size_t slot_floats, int m, int n) {
-  if (!tile_cnt) return nullptr;
-  if (!ws || slot_floats > ws_floats) return "fused split-K: slot_floats exceeds the workspace";
-  const long long t64 = (long long)((m + 63) / 64) * ((n + 63) / 64);
-  if (tile_cnt_cap < t64) return "fused split-K: fewer counters than 64^2 tiles";
-  return nullptr;
-}
-}  // namespace
-
-int mde_op_linear_res(const void* a, int lda, const void* wt, int ldw, int m, int n, int k, const float* bias, int act,
-                      const void* res0, int res0_rows, int res0_relu, const void* res1, void* out, int ldo, float* ws,
-                      size_t ws_floats, int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats, void* st) {
-  if (!a || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
-  if (res0_rows < 0 || ((res0_rows > 0 || res0_relu) && !res0)) return fail(MDE_ERR_ARG, "res0 options without res0");
-  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, m, n))
-    return fail(MDE_ERR_ARG, why);
-  GemmParams g;
-  g.A = (const h16*)a;
-  g.lda = lda;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.act = act;
-  g.res0 = (const h16*)res0;
-  g.res0_rows = res0_rows;
-  g.res0_relu = res0_relu ? 1 : 0;
-  g.res1 = (const h16*)res1;
-  g.out16 = (h16*)out;
-  g.ldo = ldo;
-  g.partial = ws;
-  g.partial_cap = ws_floats;
-  g.tile_cnt = tile_cnt;
-  g.tile_cnt_cap = tile_cnt_cap;
-  g.slot_cap = slot_floats;
-  if (slices) *slices = gemm_store_split_slices(g);
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_res");
-}
-
-int mde_op_conv3x3_res(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout, int stride,
-                       int relu_in, const float* bias, int act, const void* res0, int res0_relu, const void* res1,
-                       const void* res1_up, int res1_uh, int res1_uw, void* out, float* ws, size_t ws_floats,
-                       int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats, void* st) {
-  if (!in || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
-  if (stride != 1 && stride != 2) return fail(MDE_ERR_ARG, "stride must be 1 or 2");
-  if (res0_relu && !res0) return fail(MDE_ERR_ARG, "res0_relu without res0");
-  if (res1_up && !res1) return fail(MDE_ERR_ARG, "res1_up needs res1 (a buffer of the output's shape)");
-  GemmParams g = conv3x3_params(in, batch, h, w, cin, wt, ldw, cout, stride, relu_in, bias, act, res0, res1, out);
-  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, g.M, g.N))
-    return fail(MDE_ERR_ARG, why);
-  g.res0_relu = res0_relu ? 1 : 0;
-  g.res1_up = (const h16*)res1_up;
-  g.res1_uh = res1_uh;
-  g.res1_uw = res1_uw;
-  g.partial = ws;
-  g.partial_cap = ws_floats;
-  g.tile_cnt = tile_cnt;
-  g.tile_cnt_cap = tile_cnt_cap;
-  g.slot_cap = slot_floats;
-  if (slices) *slices = gemm_store_split_slices(g);
-  OP_RET(launch_gemm(g, (hipStream_t)st), "conv3x3_res");
-}
-
-int mde_op_linear_lnfold_tok(const void* x, const float* ln_partials, float eps, const void* wg, int ldw,
-                             const float* c1, const float* c2, int seqs, int tokens, int n, int k, int act, void* out,
-                             int ldo, void* st) {
-  if (!x || !ln_partials || !wg || !c1 || !c2 || !out) return fail(MDE_ERR_ARG, "null argument");
-  if (k & 31) return fail(MDE_ERR_ARG, "k % 32 != 0");
-  if (seqs < 1 || tokens < 2) return fail(MDE_ERR_ARG, "seqs >= 1 and tokens >= 2 (a cls row and at least one more)");
-  GemmParams g;
-  g.A = (const h16*)x;
-  g.lda = k;
-  g.W = (const h16*)wg;
-  g.ldw = ldw;
-  g.M = seqs * (tokens - 1);
-  g.N = n;
-  g.K = k;
-  g.bias = c2;
-  g.act = act;
-  g.out16 = (h16*)out;
-  g.ldo = ldo;
-  g.lnst_in = ln_partials;
-  g.lnc1 = c1;
-  g.lnst_ns = k / 32;
-  g.lnst_rows = seqs * tokens;
-  g.ln_eps = eps;
-  g.a_tok = tokens;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_lnfold_tok");
-}
-
-int mde_op_depth_head_pe(const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt, int ldw,
-                         const float* bias, const float* w2, float b2, int metric, float max_depth, const void* hpe,
-                         int hpe_pix, float* out, void* st) {
-  if (!in || !wt || !bias || !w2 || !out) return fail(MDE_ERR_ARG, "null argument");
-  if (hpe && hpe_pix < 1) return fail(MDE_ERR_ARG, "hpe needs hpe_pix >= 1");
-  GemmParams g;
-  g.amode = A_CONV3_UP;
-  g.emode = E_HEAD;
-  g.A = (const h16*)in;
-  g.cb = batch;
-  g.ch = sh;
-  g.cw = sw;
-  g.cc = cin;
-  g.uh = uh;
-  g.uw = uw;
-  g.oh = uh;
-  g.ow = uw;
-  g.stride = 1;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = batch * uh * uw;
-  g.N = 32;
-  g.K = 9 * cin;
-  g.bias = bias;
-  g.w2 = w2;
-  g.b2 = b2;
-  g.head_metric = metric;
-  g.max_depth = max_depth;
-  g.hpe = (const h16*)hpe;
-  g.hpe_pix = hpe ? hpe_pix : 0;
-  g.out32 = out;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "depth_head_pe");
-}
-
-int mde_op_conv_transpose_ld(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout,
-                             int stride, const float* bias, void* out, int ldo, void* st) {
-  if (!in || !wt || !bias || !out) return fail(MDE_ERR_ARG, "null argument");
-  GemmParams g;
-  g.emode = E_CONVT;
-  g.A = (const h16*)in;
-  g.lda = cin;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = batch * h * w;
-  g.N = stride * stride * cout;
-  g.K = cin;
-  g.bias = bias;
-  g.out16 = (h16*)out;
-  g.s = stride;
-  g.cout = cout;
-  g.ldo = ldo;
-  g.ih = h;
-  g.iw = w;
-  OP_RET(launch_gemm(g, (hipStream_t)st), "conv_transpose_ld");
-}
-
-int mde_op_linear_residual_split(const void* a, int lda, const void* wt, int ldw, int m, int n, int k,
-                                 const float* bias, const float* ls, float* x32, void* xh, int ldx, float* ln_partials,
-                                 int splitk, float* ws, size_t ws_floats, int* tile_cnt, int tile_cnt_cap,
-                                 size_t slot_floats, void* st) {
-  if (!a || !wt || !bias || !ls || (!x32 == !xh) || (!ws && ws_floats))
-    return fail(MDE_ERR_ARG, "null argument (one of x32 / xh)");
-  if (ln_partials && (!xh || (n & 31))) return fail(MDE_ERR_ARG, "ln_partials need xh and n % 32 == 0");
-  if (m < 0 || n < 0 || splitk < 0) return fail(MDE_ERR_ARG, "negative size");
-  // the 128^2 route cuts K into 4 slices whatever splitk says
-  if (splitk > 1 && (!ws || ws_floats / (size_t)(splitk > 4 ? splitk : 4) < (size_t)m * (size_t)n))
-    return fail(MDE_ERR_ARG, "ws must hold max(splitk, 4) * m * n floats");
-  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, m, n))
-    return fail(MDE_ERR_ARG, why);
-  GemmParams g;
-  g.emode = E_RESID;
-  g.A = (const h16*)a;
-  g.lda = lda;
-  g.W = (const h16*)wt;
-  g.ldw = ldw;
-  g.M = m;
-  g.N = n;
-  g.K = k;
-  g.bias = bias;
-  g.ls = ls;
-  g.x32 = x32;
-  g.xh = (h16*)xh;
-  g.ldo = ldx;
-  if (ln_partials) {
-    g.lnst_out = ln_partials;
-    g.lnst_ns = n / 32;
-    g.lnst_rows = m;
-  }
-  if (splitk > 1) {
-    g.splitk = splitk;
-    g.partial = ws;
-    g.tile_cnt = tile_cnt;
-    g.tile_cnt_cap = tile_cnt_cap;
-    g.slot_cap = slot_floats;
-  }
-  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual_split");
 }
 
 }  // extern "C"

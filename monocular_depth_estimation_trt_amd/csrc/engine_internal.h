@@ -1,10 +1,12 @@
 // Internal structures of libmde_hip's engine: the loaded packed weights
 // (mde_engine), the execution context with its activation arena
 // (mde_context) and the forward-schedule runner shared by the model
-// families (engine.hip: Depth Anything V2; depth_pro.hip: Depth Pro).
+// families (engine.hip: Depth Anything V2 and the shared transformer block /
+// DPT decoder steps; depth_pro.hip: Depth Pro; vggt.hip: VGGT).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mde.h"
+#include "gemm_params.h"
 #include "mde_ops.h"
 #include "pack_format.h"
 #include "tuning.h"
@@ -28,13 +31,19 @@ struct DevTensor {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// NHWC f16 maps of the DPT decoder over n images / frames (plan_dpt_maps)
+struct DptMaps {
+  h16 *pj[4], *l1, *l2, *l4, *rn[4];
+  h16 *tb, *sb, *ub, *vb, *p4, *p3, *p2, *c1;
+};
+
 // Depth Anything V2 activations (engine.hip plan_arena_dav2)
 struct DAV2Buf {
   h16 *P, *Hn, *Q, *K, *Vt, *O, *Mh;
   float* X;   // fp32 residual stream [B*T][D] (null when Xh is used)
   h16* Xh;    // f16 residual stream (packed precision "fp16", cfg.resid_f16), else null
-  h16 *tap[4], *pj[4], *l1, *l2, *l4, *rn[4];
-  h16 *tb, *sb, *ub, *vb, *p4, *p3, *p2, *c1;
+  h16* tap[4];
+  DptMaps m;
   float* ws;        // fc2 split-K partials [4][B*T][D] (small-batch contexts only, else null)
   float* aws;       // attention split-KV partials (batches whose grid splits, else null)
   size_t aws_bytes;
@@ -92,8 +101,7 @@ struct VGBuf {
   h16 *Q, *K, *Vt;         // frame attention operands [n*H][Tpad][64]
   h16 *Qg, *Kg, *Vg;       // global attention operands [B*H][Tgpad][64] (alias Q/K/Vt when S == 1)
   h16* tap;                // LN(cat(frame, global)) patch tokens [n*np][2D]
-  h16 *pj[4], *l1, *l2, *l4, *rn[4];
-  h16 *tb, *sb, *ub, *vb, *p4, *p3, *p2, *c1;
+  DptMaps m;
   float* ws;               // fc2 split-K partials [4][ws_rows][D] (small-batch contexts only, else null)
   size_t ws_rows;
   float* sws;              // E_STORE split-K partials (kSplitWsFloats)
@@ -195,10 +203,36 @@ struct ArenaPlan {
 size_t plan_arena_dav2(const mde_engine& e, int B, DAV2Buf* b, uint8_t* base);
 size_t plan_arena_dp(const mde_engine& e, int B, DPBuf* b, uint8_t* base);
 size_t plan_arena_vggt(const mde_engine& e, int B, VGBuf* b, uint8_t* base);
+// the DPT decoder's maps over n images / frames (engine.hip)
+DptMaps plan_dpt_maps(ArenaPlan& a, size_t n, const mde_engine& e);
 // Load-time checks (tensor presence, supported geometry); fill the derived
 // geometry.  Return an error message or "".
 std::string setup_depth_pro(mde_engine* e);
 std::string setup_vggt(mde_engine* e);
+
+// What differs between the families' f16 transformer blocks (Runner::vit_block):
+// norm1 -> qkv -> attention -> proj -> norm2 -> fc1 (GELU) -> fc2 over `seqs`
+// sequences of T tokens, width D and head count of the engine.
+struct VitBlock {
+  std::string w;     // weight-name prefix ("b3.", "pe.b3.", "fb3.")
+  std::string name;  // step-name prefix ("block3.", "pe.block3.", "fb3.")
+  int seqs = 0, T = 0, Tpad = 0;
+  float eps = 1e-6f, qscale = kQScale;
+  float* X = nullptr;  // residual stream [seqs * T][D]: fp32, or
+  h16* Xh = nullptr;   // f16 (then X is null)
+  h16 *Hn = nullptr, *Q = nullptr, *K = nullptr, *Vt = nullptr, *O = nullptr, *Mh = nullptr;  // scratch
+  // LayerNorm folded across the GEMM boundary (packs with folded weights): the
+  // residual writers' row partials; null: LayerNorm launches + the unfolded linears
+  float* st = nullptr;
+  float* aws = nullptr;  // attention split-KV workspace (optional)
+  size_t aws_bytes = 0;
+  // fc2 split-K partials [4][ws_rows][D] and their arrival counters (null: fc2 never splits)
+  float* ws = nullptr;
+  size_t ws_rows = 0;
+  int* counters = nullptr;
+  // run between qkv and attention (VGGT's q/k norm + RoPE step)
+  std::function<void()> after_qkv;
+};
 
 // The forward schedule: one method per model family, common helpers here.
 struct Runner {
@@ -238,53 +272,18 @@ struct Runner {
   int ldw(const std::string& n) { return W(n).dims[W(n).ndim - 1]; }
 
   GemmParams dense(const h16* A, int lda, const std::string& w, int M, int N, int K) {
-    GemmParams g;
-    g.amode = A_DENSE;
-    g.A = A;
-    g.lda = lda;
-    g.W = w16(w);
-    g.ldw = ldw(w);
-    g.M = M;
-    g.N = N;
-    g.K = K;
-    return g;
+    return gemm_dense(A, lda, w16(w), ldw(w), M, N, K);
   }
 
   // 3x3 pad-1 conv over NHWC map [B][h][w][cin] -> [B][ho][wo][cout]
   GemmParams conv(const h16* in, int B, int h, int w, int cin, const std::string& wn, int cout, int stride) {
-    GemmParams g;
-    g.amode = A_CONV3;
-    g.A = in;
-    g.cb = B;
-    g.ch = h;
-    g.cw = w;
-    g.cc = cin;
-    g.stride = stride;
-    g.oh = (h - 1) / stride + 1;
-    g.ow = (w - 1) / stride + 1;
-    g.W = w16(wn);
-    g.ldw = ldw(wn);
-    g.M = B * g.oh * g.ow;
-    g.N = cout;
-    g.K = 9 * cin;
-    g.out16 = nullptr;
-    g.ldo = cout;
-    return g;
+    return gemm_conv3(in, B, h, w, cin, w16(wn), ldw(wn), cout, stride);
   }
 
-  // ConvTranspose(k = s = 2) of an NHWC map as a GEMM with a pixel-shuffle
-  // epilogue; ldo = channel stride of the output map (concat slots)
+  // ConvTranspose(k = s = 2) of an NHWC map; ldo = channel stride of the output map (concat slots)
   GemmParams convt2(const h16* in, int B, int h, int w, int cin, const std::string& wn, int cout, h16* out,
                     int ldo) {
-    GemmParams g = dense(in, cin, wn, B * h * w, 4 * cout, cin);
-    g.emode = E_CONVT;
-    g.out16 = out;
-    g.s = 2;
-    g.cout = cout;
-    g.ldo = ldo;
-    g.ih = h;
-    g.iw = w;
-    return g;
+    return gemm_convt(in, B, h, w, cin, w16(wn), ldw(wn), cout, 2, out, ldo);
   }
 
   // E_STORE split-K workspace for launch_gemm's small-grid policy (null: never split)
@@ -383,14 +382,29 @@ struct Runner {
     gemm((pfx + ".c2").c_str(), g2);
   }
 
+  // the f16 transformer block of every family (engine.hip)
+  void vit_block(const VitBlock& b);
+
+  // DPT decoder steps over the maps m of n images / frames (engine.hip); each
+  // family's forward runs them in its own order.  Level i in 0..3 is the map
+  // of tap i, dpt_h(i) x dpt_w(i): 4x, 2x, 1x the patch grid and its stride-2 half.
+  int dpt_h(int i) const { return i == 0 ? 4 * c.e->ph : i == 1 ? 2 * c.e->ph : i == 2 ? c.e->ph : c.e->h4; }
+  int dpt_w(int i) const { return i == 0 ? 4 * c.e->pw : i == 1 ? 2 * c.e->pw : i == 2 ? c.e->pw : c.e->w4; }
+  void dpt_resize_layer(DptMaps& m, int n, int i);
+  void dpt_layer_rn(DptMaps& m, int n, int i);
+  bool dpt_fusion(DptMaps& m, int n, int r, bool relu_res, bool fold_resize, const h16* x0_up = nullptr, int uh = 0,
+                  int uw = 0);
+  void dpt_head_conv1(DptMaps& m, int n);
+  void dpt_head_conv2(DptMaps& m, int n, int metric, float max_depth, const h16* hpe, int hpe_pix, float* out);
+
   hipError_t forward_dav2(int B, const void* img, float* out);
-  bool dav2_fusion(int r, const h16* x0, const h16* x1, int B, int h, int w, h16* dst, int oh, int ow,
-                   const h16* x0_up = nullptr, int uh = 0, int uw = 0);
   hipError_t forward_dp(int B, const float* img, float* out, float* fov);
   void dp_encoder(const std::string& pfx, float* X, const h16* P, int nseq, int hook_seqs);
   hipError_t forward_vggt(int B, const float* img, float* out);
-  void vggt_block(const std::string& p, float eps, bool qk, int seqs, int T, int Tpad, h16* Q, h16* K, h16* Vt);
-  void vggt_fusion(int r, const h16* x0, const h16* x1, int n, int h, int w, h16* dst, int oh, int ow);
 };
+
+// set the thread's mde_last_error message; return `code` / MDE_ERR_HIP (engine.hip)
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* what);
 
 }  // namespace mde

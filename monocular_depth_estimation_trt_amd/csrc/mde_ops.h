@@ -207,7 +207,7 @@ hipError_t launch_resize_u8(const unsigned char* src, int B, int sh, int sw, int
 // align_corners=False -> float NCHW [B][3][oh][ow]; lut float[256]) and post-process (inverse depth
 // [B][ih][iw] * ow / f, the same bilinear to [B][oh][ow], 1 / clamp(., 1e-4, 1e4); f from fov_deg [B]
 // when non-null, else f_px; f_px_out [B] optional).  No argument checks here: the ABI wrappers in
-// engine.hip hold the only copy of the limits
+// ops_abi.hip hold the only copy of the limits
 hipError_t launch_dp_preprocess(const unsigned char* src, int B, int sh, int sw, int pitch, int swap_rb,
                                 const float* lut, float* dst, int oh, int ow, hipStream_t st);
 hipError_t launch_dp_postprocess(const float* inv, int B, int ih, int iw, const float* fov_deg, float f_px,

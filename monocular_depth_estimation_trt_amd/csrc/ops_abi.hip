@@ -1,0 +1,628 @@
+// libmde_hip op-level C ABI (include/mde.h mde_op_*): one kernel launch per
+// entry point, for the parity tests and tools.  Host code only: argument
+// validation here, launch parameters through the builders the engines use
+// (gemm_params.h), kernels and dispatch policy in the launchers.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "engine_internal.h"
+
+using namespace mde;
+
+extern "C" {
+
+// ---- kernel-level entry points ------------------------------------------------
+// a launcher's result as the ABI status: hipErrorInvalidValue is the
+// launchers' "bad shape / argument", anything else a HIP failure
+static int op_status(hipError_t e, const char* what) {
+  if (e == hipErrorInvalidValue) return fail(MDE_ERR_ARG, std::string(what) + ": invalid shape/argument");
+  if (e != hipSuccess) return hip_fail(e, what);
+  return MDE_OK;
+}
+#define OP_RET(call, what) return op_status((call), what)
+
+int mde_op_patch_prep_u8(const unsigned char* img, int batch, int h, int w, float scale, const float* mean3,
+                         const float* std3, void* patches, void* st) {
+  if (!img || !mean3 || !std3 || !patches || batch < 1 || h % 14 || w % 14 || h < 14 || w < 14)
+    return fail(MDE_ERR_ARG, "mde_op_patch_prep_u8: bad argument (h, w multiples of 14)");
+  OP_RET(launch_patch_prep_u8(img, (h16*)patches, nullptr, nullptr, batch, h, w, h / 14, w / 14, 1, 0, scale, mean3,
+                              std3, (hipStream_t)st),
+         "patch_prep_u8");
+}
+
+int mde_op_depth_postprocess(const float* depth, int batch, int ih, int iw, float* out, int oh, int ow, float lo,
+                             float hi, void* st) {
+  if (!depth || !out || batch < 1 || ih < 1 || iw < 1 || oh < 1 || ow < 1)
+    return fail(MDE_ERR_ARG, "mde_op_depth_postprocess: bad argument");
+  OP_RET(launch_depth_postprocess(depth, batch, ih, iw, out, oh, ow, lo, hi, (hipStream_t)st), "depth_postprocess");
+}
+
+namespace {
+const char* resize_u8_arg_error(const void* src, const void* dst, int batch, int sh, int sw, int pitch, int oh,
+                                int ow) {
+  if (!src || !dst) return "null pointer";
+  if (batch < 1 || sh < 1 || sw < 1 || oh < 1 || ow < 1) return "batch and sizes must be positive";
+  if (pitch < 3 * (long long)sw) return "pitch < 3 * sw";
+  return nullptr;
+}
+}  // namespace
+
+int mde_op_resize_u8(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                     unsigned char* dst_u8, int oh, int ow, void* st) {
+  if (const char* why = resize_u8_arg_error(src, dst_u8, batch, sh, sw, pitch, oh, ow))
+    return fail(MDE_ERR_ARG, std::string("mde_op_resize_u8: ") + why);
+  OP_RET(launch_resize_u8(src, batch, sh, sw, pitch, swap_rb, nullptr, dst_u8, oh, ow, (hipStream_t)st),
+         "mde_op_resize_u8");
+}
+
+int mde_op_resize_u8_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                          const float* lut3x256, float* dst_f32_nchw, int oh, int ow, void* st) {
+  const char* why = resize_u8_arg_error(src, dst_f32_nchw, batch, sh, sw, pitch, oh, ow);
+  if (!why && !lut3x256) why = "null pointer";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_resize_u8_norm: ") + why);
+  OP_RET(launch_resize_u8(src, batch, sh, sw, pitch, swap_rb, lut3x256, dst_f32_nchw, oh, ow, (hipStream_t)st),
+         "mde_op_resize_u8_norm");
+}
+
+namespace {
+// the Depth Pro photo ops index a plane with an int and put the batch on grid.y
+const char* dp_photo_geometry_error(int batch, int sh, int sw, int oh, int ow) {
+  if (batch < 1 || sh < 1 || sw < 1 || oh < 1 || ow < 1) return "batch and sizes must be positive";
+  const long long lim = 0x7fffffffLL - 256;
+  if ((long long)sh * sw >= lim || (long long)oh * ow >= lim) return "a plane of 2^31 - 256 elements or more";
+  if (batch > 65535) return "batch > 65535";
+  return nullptr;
+}
+}  // namespace
+
+int mde_op_dp_preprocess(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                         const float* lut256, float* dst_f32_nchw, int oh, int ow, void* st) {
+  const char* why = dp_photo_geometry_error(batch, sh, sw, oh, ow);
+  if (!src || !lut256 || !dst_f32_nchw) why = "null pointer";
+  if (!why && pitch < 3 * (long long)sw) why = "pitch < 3 * sw";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_dp_preprocess: ") + why);
+  OP_RET(launch_dp_preprocess(src, batch, sh, sw, pitch, swap_rb, lut256, dst_f32_nchw, oh, ow, (hipStream_t)st),
+         "mde_op_dp_preprocess");
+}
+
+int mde_op_dp_postprocess(const float* inv, int batch, int ih, int iw, const float* fov_deg, float f_px,
+                          float* f_px_out, float* depth, int oh, int ow, void* st) {
+  const char* why = (!inv || !depth) ? "null pointer" : dp_photo_geometry_error(batch, ih, iw, oh, ow);
+  if (!why && !fov_deg && !(f_px > 0.f)) why = "fov_deg is null and f_px <= 0";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_dp_postprocess: ") + why);
+  OP_RET(launch_dp_postprocess(inv, batch, ih, iw, fov_deg, f_px, f_px_out, depth, oh, ow, (hipStream_t)st),
+         "mde_op_dp_postprocess");
+}
+
+int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
+  if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
+  DpPyramid pyr;
+  pyr.nlev = 3;
+  const int f[3] = {1, 2, 4}, n[3] = {5, 3, 1}, stride[3] = {288, 192, 384};
+  int first = 0;
+  for (int i = 0; i < 3; ++i) {
+    pyr.first[i] = first;
+    pyr.n[i] = n[i];
+    pyr.stride[i] = stride[i];
+    pyr.f[i] = f[i];
+    first += n[i] * n[i];
+  }
+  pyr.nseq = first;
+  OP_RET(launch_dp_patch_prep(img, (h16*)patches, batch, size, 24, pyr, (hipStream_t)st), "dp_pyramid_patches");
+}
+
+int mde_op_merge_tokens(const float* x32, int batch, int tokens, int dim, int n, int g, int pad, int base,
+                        const float* gamma, const float* beta, float eps, void* out, void* st) {
+  if (!x32 || !out || batch < 1 || (gamma == nullptr) != (beta == nullptr))
+    return fail(MDE_ERR_ARG, "mde_op_merge_tokens: bad argument");
+  DpMerge m;
+  m.B = batch;
+  m.n = n;
+  m.G = g;
+  m.pad = pad;
+  m.base = base;
+  m.T = tokens;
+  OP_RET(launch_merge_tokens(x32, (h16*)out, gamma, beta, dim, m, eps, (hipStream_t)st), "merge_tokens");
+}
+
+int mde_op_qk_norm_rope(void* q, void* k, const float* qg, const float* qb, const float* kg, const float* kb, int bh,
+                        int tokens, int tokens_pad, int frame_tokens, int npre, int grid_w, const float* rope_cos,
+                        const float* rope_sin, float q_scale, float eps, void* st) {
+  if (!q || !k || !qg || !qb || !kg || !kb || !rope_cos || !rope_sin) return fail(MDE_ERR_ARG, "null argument");
+  RopeGeom geo;
+  geo.T = tokens;
+  geo.Tpad = tokens_pad;
+  geo.P = frame_tokens;
+  geo.npre = npre;
+  geo.gw = grid_w;
+  geo.qscale = q_scale;
+  geo.eps = eps;
+  OP_RET(launch_qk_norm_rope((h16*)q, (h16*)k, qg, qb, kg, kb, rope_cos, rope_sin, bh, geo, (hipStream_t)st),
+         "qk_norm_rope");
+}
+
+int mde_op_tap_concat_ln(const float* xa, const float* xb, int nseq, int tokens, int npre, int dim, const float* g,
+                         const float* b, float eps, void* out, void* st) {
+  if (!xa || !xb || !g || !b || !out || nseq < 0) return fail(MDE_ERR_ARG, "null argument");
+  OP_RET(launch_tap_concat_ln(xa, xb, (h16*)out, g, b, nseq, tokens, npre, dim, eps, (hipStream_t)st),
+         "tap_concat_ln");
+}
+
+int mde_op_layernorm_f16(const void* x, void* y, const float* g, const float* b, int rows, int dim, float eps,
+                         int tokens, int skip_cls, void* st) {
+  if (!x || !y || !g || !b) return fail(MDE_ERR_ARG, "null argument");
+  if (skip_cls && tokens < 2) return fail(MDE_ERR_ARG, "skip_cls needs tokens >= 2");
+  OP_RET(launch_layernorm(nullptr, (h16*)y, g, b, rows, dim, eps, tokens > 0 ? tokens : 1, skip_cls, (hipStream_t)st,
+                          (const h16*)x),
+         "layernorm_f16");
+}
+
+int mde_op_layernorm(const float* x, void* y, const float* g, const float* b, int rows, int dim, float eps,
+                     int tokens, int skip_cls, void* st) {
+  if (!x || !y || !g || !b) return fail(MDE_ERR_ARG, "null argument");
+  if (skip_cls && tokens < 2) return fail(MDE_ERR_ARG, "skip_cls needs tokens >= 2");
+  OP_RET(launch_layernorm(x, (h16*)y, g, b, rows, dim, eps, tokens > 0 ? tokens : 1, skip_cls, (hipStream_t)st),
+         "layernorm");
+}
+
+namespace {
+// fused split-K operands (GemmParams::tile_cnt): the slots live in ws, and
+// every 64^2 tile of the problem has a counter (the 128^2 grids are smaller)
+const char* fused_split_error(const float* ws, size_t ws_floats, const int* tile_cnt, int tile_cnt_cap,
+                              size_t slot_floats, int m, int n) {
+  if (!tile_cnt) return nullptr;
+  if (!ws || slot_floats > ws_floats) return "fused split-K: slot_floats exceeds the workspace";
+  const long long t64 = (long long)((m + 63) / 64) * ((n + 63) / 64);
+  if (tile_cnt_cap < t64) return "fused split-K: fewer counters than 64^2 tiles";
+  return nullptr;
+}
+
+// E_STORE split-K operands of the *_ws / *_res entry points; reports the slice count
+void set_store_split(GemmParams& g, float* ws, size_t ws_floats, int* slices, int* tile_cnt, int tile_cnt_cap,
+                     size_t slot_floats) {
+  g.partial = ws;
+  g.partial_cap = ws_floats;
+  g.tile_cnt = tile_cnt;
+  g.tile_cnt_cap = tile_cnt_cap;
+  g.slot_cap = slot_floats;
+  if (slices) *slices = gemm_store_split_slices(g);
+}
+
+// mde_op_linear_res and its subsets mde_op_linear_ws, mde_op_linear (the options they lack off)
+int linear_store(const char* what, const void* a, int lda, const void* wt, int ldw, int m, int n, int k,
+                 const float* bias, int act, const void* res0, int res0_rows, int res0_relu, const void* res1,
+                 void* out, int ldo, float* ws, size_t ws_floats, int* slices, int* tile_cnt, int tile_cnt_cap,
+                 size_t slot_floats, void* st) {
+  if (!a || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
+  if (res0_rows < 0 || ((res0_rows > 0 || res0_relu) && !res0)) return fail(MDE_ERR_ARG, "res0 options without res0");
+  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, m, n))
+    return fail(MDE_ERR_ARG, why);
+  GemmParams g = gemm_dense((const h16*)a, lda, (const h16*)wt, ldw, m, n, k);
+  g.bias = bias;
+  g.act = act;
+  g.res0 = (const h16*)res0;
+  g.res0_rows = res0_rows;
+  g.res0_relu = res0_relu ? 1 : 0;
+  g.res1 = (const h16*)res1;
+  g.out16 = (h16*)out;
+  g.ldo = ldo;
+  set_store_split(g, ws, ws_floats, slices, tile_cnt, tile_cnt_cap, slot_floats);
+  return op_status(launch_gemm(g, (hipStream_t)st), what);
+}
+
+// mde_op_conv3x3_res and its subsets mde_op_conv3x3_ws, mde_op_conv3x3
+int conv3x3_store(const char* what, const void* in, int batch, int h, int w, int cin, const void* wt, int ldw,
+                  int cout, int stride, int relu_in, const float* bias, int act, const void* res0, int res0_relu,
+                  const void* res1, const void* res1_up, int res1_uh, int res1_uw, void* out, float* ws,
+                  size_t ws_floats, int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats, void* st) {
+  if (!in || !wt || !out || (!ws && ws_floats)) return fail(MDE_ERR_ARG, "null argument");
+  if (stride != 1 && stride != 2) return fail(MDE_ERR_ARG, "stride must be 1 or 2");
+  if (res0_relu && !res0) return fail(MDE_ERR_ARG, "res0_relu without res0");
+  if (res1_up && !res1) return fail(MDE_ERR_ARG, "res1_up needs res1 (a buffer of the output's shape)");
+  GemmParams g = gemm_conv3((const h16*)in, batch, h, w, cin, (const h16*)wt, ldw, cout, stride);
+  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, g.M, g.N))
+    return fail(MDE_ERR_ARG, why);
+  g.relu_in = relu_in;
+  g.bias = bias;
+  g.act = act;
+  g.res0 = (const h16*)res0;
+  g.res0_relu = res0_relu ? 1 : 0;
+  g.res1 = (const h16*)res1;
+  g.res1_up = (const h16*)res1_up;
+  g.res1_uh = res1_uh;
+  g.res1_uw = res1_uw;
+  g.out16 = (h16*)out;
+  set_store_split(g, ws, ws_floats, slices, tile_cnt, tile_cnt_cap, slot_floats);
+  return op_status(launch_gemm(g, (hipStream_t)st), what);
+}
+}  // namespace
+
+int mde_op_linear(const void* a, int lda, const void* w, int ldw, int m, int n, int k, const float* bias, int act,
+                  void* out, int ldo, void* st) {
+  return linear_store("linear", a, lda, w, ldw, m, n, k, bias, act, nullptr, 0, 0, nullptr, out, ldo, nullptr, 0,
+                      nullptr, nullptr, 0, 0, st);
+}
+
+int mde_op_linear_residual(const void* a, int lda, const void* w, int ldw, int m, int n, int k, const float* bias,
+                           const float* ls, float* x32, int ldx, void* st) {
+  if (!a || !w || !bias || !ls || !x32) return fail(MDE_ERR_ARG, "null argument");
+  GemmParams g = gemm_dense((const h16*)a, lda, (const h16*)w, ldw, m, n, k);
+  set_resid(g, bias, ls, x32, nullptr, ldx);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual");
+}
+
+// E_QKV geometry: V^T stores key t at vt_pos(t), which swaps bits 2 and 3 of
+// t, so a row of tokens_pad keys holds whole 16-key groups only when
+// tokens_pad % 16 == 0 (otherwise the last group's keys land in the next row)
+static const char* qkv_geometry_error(int batch, int tokens, int heads, int tokens_pad) {
+  if (batch <= 0 || tokens <= 0 || heads <= 0) return "batch, tokens and heads must be > 0";
+  if (tokens_pad < tokens) return "tokens_pad < tokens";
+  if (tokens_pad % 16) return "tokens_pad % 16 != 0 (V^T key permutation works on 16-key groups)";
+  return nullptr;
+}
+
+int mde_op_qkv(const void* a, const void* w, int ldw, const float* bias, int batch, int tokens, int heads,
+               int tokens_pad, float qscale, void* q, void* k, void* vt, void* st) {
+  if (!a || !w || !bias || !q || !k || !vt) return fail(MDE_ERR_ARG, "null argument");
+  if (const char* why = qkv_geometry_error(batch, tokens, heads, tokens_pad)) return fail(MDE_ERR_ARG, why);
+  const int D = heads * 64;
+  GemmParams g = gemm_dense((const h16*)a, D, (const h16*)w, ldw, batch * tokens, 3 * D, D);
+  g.bias = bias;
+  set_qkv(g, (h16*)q, (h16*)k, (h16*)vt, tokens, tokens_pad, heads, qscale);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "qkv");
+}
+
+int mde_op_linear_residual_f16(const void* a, int lda, const void* w, int ldw, int m, int n, int k, const float* bias,
+                               const float* ls, void* xh, int ldx, float* ln_partials, void* st) {
+  if (!a || !w || !bias || !ls || !xh) return fail(MDE_ERR_ARG, "null argument");
+  if (ln_partials && (n & 31)) return fail(MDE_ERR_ARG, "ln_partials need n % 32 == 0");
+  GemmParams g = gemm_dense((const h16*)a, lda, (const h16*)w, ldw, m, n, k);
+  set_resid(g, bias, ls, nullptr, (h16*)xh, ldx);
+  set_ln_producer(g, ln_partials, m);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual_f16");
+}
+
+namespace {
+// mde_op_linear_lnfold_tok (a_tok = tokens: every sequence's cls row skipped)
+// and its subset mde_op_linear_lnfold (a_tok = 0, lnst_rows = m)
+int linear_lnfold(const char* what, const void* x, const float* ln_partials, float eps, const void* wg, int ldw,
+                  const float* c1, const float* c2, int m, int n, int k, int act, void* out, int ldo, int lnst_rows,
+                  int a_tok, void* st) {
+  GemmParams g = gemm_dense((const h16*)x, k, (const h16*)wg, ldw, m, n, k);
+  g.act = act;
+  g.out16 = (h16*)out;
+  g.ldo = ldo;
+  set_ln_consumer(g, ln_partials, c1, c2, lnst_rows, eps);
+  g.a_tok = a_tok;
+  return op_status(launch_gemm(g, (hipStream_t)st), what);
+}
+}  // namespace
+
+int mde_op_linear_lnfold(const void* x, const float* ln_partials, float eps, const void* wg, int ldw, const float* c1,
+                         const float* c2, int m, int n, int k, int act, void* out, int ldo, void* st) {
+  if (!x || !ln_partials || !wg || !c1 || !c2 || !out) return fail(MDE_ERR_ARG, "null argument");
+  if (k & 31) return fail(MDE_ERR_ARG, "k % 32 != 0");
+  return linear_lnfold("linear_lnfold", x, ln_partials, eps, wg, ldw, c1, c2, m, n, k, act, out, ldo, m, 0, st);
+}
+
+int mde_op_qkv_lnfold(const void* x, const float* ln_partials, float eps, const void* wg, int ldw, const float* c1,
+                      const float* c2, int batch, int tokens, int heads, int tokens_pad, float qscale, void* q, void* k,
+                      void* vt, void* st) {
+  if (!x || !ln_partials || !wg || !c1 || !c2 || !q || !k || !vt) return fail(MDE_ERR_ARG, "null argument");
+  if (const char* why = qkv_geometry_error(batch, tokens, heads, tokens_pad)) return fail(MDE_ERR_ARG, why);
+  const int D = heads * 64;
+  GemmParams g = gemm_dense((const h16*)x, D, (const h16*)wg, ldw, batch * tokens, 3 * D, D);
+  set_qkv(g, (h16*)q, (h16*)k, (h16*)vt, tokens, tokens_pad, heads, qscale);
+  set_ln_consumer(g, ln_partials, c1, c2, g.M, eps);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "qkv_lnfold");
+}
+
+int mde_op_attention(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int tokens,
+                     int tokens_pad, int ldo, void* st) {
+  if (!q || !k || !vt || !o) return fail(MDE_ERR_ARG, "null argument");
+  OP_RET(launch_attention((const h16*)q, (const h16*)k, (const h16*)vt, (h16*)o, batch, heads, tokens, tokens_pad,
+                          ldo, (hipStream_t)st),
+         "attention");
+}
+
+int mde_op_attention_ws(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int tokens,
+                        int tokens_pad, int ldo, void* ws, size_t ws_bytes, void* st) {
+  if (!q || !k || !vt || !o || (!ws && ws_bytes)) return fail(MDE_ERR_ARG, "null argument");
+  OP_RET(launch_attention((const h16*)q, (const h16*)k, (const h16*)vt, (h16*)o, batch, heads, tokens, tokens_pad,
+                          ldo, (hipStream_t)st, (float*)ws, ws_bytes),
+         "attention_ws");
+}
+
+int mde_op_attention_cfg(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int tokens,
+                         int tokens_pad, int ldo, const char* cfg, void* ws, size_t ws_bytes, void* st) {
+  if (!q || !k || !vt || !o || (!ws && ws_bytes)) return fail(MDE_ERR_ARG, "null argument");
+  OP_RET(launch_attention((const h16*)q, (const h16*)k, (const h16*)vt, (h16*)o, batch, heads, tokens, tokens_pad,
+                          ldo, (hipStream_t)st, (float*)ws, ws_bytes, cfg),
+         "attention_cfg");
+}
+
+size_t mde_op_attention_ws_bytes(int batch, int heads, int tokens) {
+  return batch > 0 && heads > 0 && tokens > 0 ? attention_split_ws_bytes(batch, heads, tokens) : 0;
+}
+
+int mde_op_linear32(const float* a, int lda, const float* w, int ldw, int m, int n, int k, const float* bias, int act,
+                    float* out, int ldo, void* st) {
+  if (!a || !w || !out) return fail(MDE_ERR_ARG, "null argument");
+  Gemm32Params g;
+  g.A = a;
+  g.lda = lda;
+  g.W = w;
+  g.ldw = ldw;
+  g.M = m;
+  g.N = n;
+  g.K = k;
+  g.bias = bias;
+  g.act = act;
+  g.out32 = out;
+  g.ldo = ldo;
+  OP_RET(launch_gemm32(g, (hipStream_t)st), "linear32");
+}
+
+int mde_op_conv3x3_32(const float* in, int batch, int h, int w, int cin, const float* wt, int ldw, int cout,
+                      int stride, int relu_in, const float* bias, int act, const float* res0, const float* res1,
+                      float* out, void* st) {
+  if (!in || !wt || !out) return fail(MDE_ERR_ARG, "null argument");
+  if (stride != 1 && stride != 2) return fail(MDE_ERR_ARG, "stride must be 1 or 2");
+  if (batch <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return fail(MDE_ERR_ARG, "bad shape");
+  Gemm32Params g;
+  g.amode = A_CONV3;
+  g.emode = E_STORE;
+  g.A = in;
+  g.cb = batch;
+  g.ch = h;
+  g.cw = w;
+  g.cc = cin;
+  g.stride = stride;
+  g.oh = (h - 1) / stride + 1;
+  g.ow = (w - 1) / stride + 1;
+  g.W = wt;
+  g.ldw = ldw;
+  g.M = batch * g.oh * g.ow;
+  g.N = cout;
+  g.K = 9 * cin;
+  g.relu_in = relu_in;
+  g.bias = bias;
+  g.act = act;
+  g.res0 = res0;
+  g.res1 = res1;
+  g.out32 = out;
+  g.ldo = cout;
+  OP_RET(launch_gemm32(g, (hipStream_t)st), "conv3x3_32");
+}
+
+int mde_op_conv_transpose32(const float* in, int batch, int h, int w, int cin, const float* wt, int ldw, int cout,
+                            int stride, const float* bias, float* out, void* st) {
+  if (!in || !wt || !out) return fail(MDE_ERR_ARG, "null argument");
+  if (batch <= 0 || h <= 0 || w <= 0 || stride < 1) return fail(MDE_ERR_ARG, "bad shape");
+  Gemm32Params g;
+  g.emode = E_CONVT;
+  g.A = in;
+  g.lda = cin;
+  g.W = wt;
+  g.ldw = ldw;
+  g.M = batch * h * w;
+  g.N = stride * stride * cout;
+  g.K = cin;
+  g.bias = bias;
+  g.out32 = out;
+  g.ldo = cout;
+  g.s = stride;
+  g.cout = cout;
+  g.cb = batch;
+  g.ih = h;
+  g.iw = w;
+  OP_RET(launch_gemm32(g, (hipStream_t)st), "conv_transpose32");
+}
+
+int mde_op_resize32(const float* in, int batch, int h, int w, int c, int oh, int ow, float* out, void* st) {
+  if (!in || !out) return fail(MDE_ERR_ARG, "null argument");
+  OP_RET(launch_resize32(in, out, batch, h, w, c, oh, ow, (hipStream_t)st), "resize32");
+}
+
+int mde_op_linear_residual32(const float* a, int lda, const float* w, int ldw, int m, int n, int k,
+                             const float* bias, const float* ls, float* x32, int ldx, void* st) {
+  if (!a || !w || !ls || !x32) return fail(MDE_ERR_ARG, "null argument");
+  Gemm32Params g;
+  g.emode = E_RESID;
+  g.A = a;
+  g.lda = lda;
+  g.W = w;
+  g.ldw = ldw;
+  g.M = m;
+  g.N = n;
+  g.K = k;
+  g.bias = bias;
+  g.ls = ls;
+  g.x32 = x32;
+  g.ldo = ldx;
+  OP_RET(launch_gemm32(g, (hipStream_t)st), "linear_residual32");
+}
+
+int mde_op_qkv32(const float* a, const float* w, int ldw, const float* bias, int batch, int tokens, int heads,
+                 int tokens_pad, float q_scale, float* q, float* k, float* v, void* st) {
+  if (!a || !w || !q || !k || !v) return fail(MDE_ERR_ARG, "null argument");
+  Gemm32Params g;
+  g.emode = E_QKV;
+  g.A = a;
+  g.lda = heads * 64;
+  g.W = w;
+  g.ldw = ldw;
+  g.M = batch * tokens;
+  g.N = 3 * heads * 64;
+  g.K = heads * 64;
+  g.bias = bias;
+  g.q = q;
+  g.k = k;
+  g.v = v;
+  g.T = tokens;
+  g.Tpad = tokens_pad;
+  g.heads = heads;
+  g.qscale = q_scale;
+  OP_RET(launch_gemm32(g, (hipStream_t)st), "qkv32");
+}
+
+int mde_op_attention32(const float* q, const float* k, const float* v, float* o, int batch, int heads, int tokens,
+                       int tokens_pad, int ldo, void* st) {
+  if (!q || !k || !v || !o) return fail(MDE_ERR_ARG, "null argument");
+  OP_RET(launch_attention32(q, k, v, o, batch, heads, tokens, tokens_pad, ldo, (hipStream_t)st), "attention32");
+}
+
+int mde_op_patch_embed(const float* img, int batch, int h, int w, const void* wt, int ldw, const float* bias,
+                       const float* pos_patch, const float* cls_pos, int dim, void* scratch, float* x32, void* st) {
+  if (!img || !wt || !bias || !pos_patch || !cls_pos || !scratch || !x32) return fail(MDE_ERR_ARG, "null argument");
+  if (h % 14 || w % 14) return fail(MDE_ERR_ARG, "image size must be a multiple of 14");
+  const int ph = h / 14, pw = w / 14, T = ph * pw + 1;
+  hipError_t e = launch_patch_prep(img, (h16*)scratch, x32, cls_pos, batch, h, w, ph, pw, T, dim, (hipStream_t)st);
+  if (e != hipSuccess) return hip_fail(e, "patch_prep");
+  GemmParams g = gemm_dense((const h16*)scratch, 672, (const h16*)wt, ldw, batch * ph * pw, dim, 672);
+  g.emode = E_PATCH;
+  g.bias = bias;
+  g.x32 = x32;
+  g.ldo = dim;
+  g.T = T;
+  g.pos = pos_patch;
+  g.npatch = ph * pw;
+  OP_RET(launch_gemm(g, (hipStream_t)st), "patch_embed");
+}
+
+int mde_op_conv3x3(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout, int stride,
+                   int relu_in, const float* bias, int act, const void* res0, const void* res1, void* out,
+                   void* st) {
+  return conv3x3_store("conv3x3", in, batch, h, w, cin, wt, ldw, cout, stride, relu_in, bias, act, res0, 0, res1,
+                       nullptr, 0, 0, out, nullptr, 0, nullptr, nullptr, 0, 0, st);
+}
+
+int mde_op_conv3x3_ws(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout, int stride,
+                      int relu_in, const float* bias, int act, const void* res0, const void* res1, void* out,
+                      float* ws, size_t ws_floats, int* slices, void* st) {
+  return conv3x3_store("conv3x3_ws", in, batch, h, w, cin, wt, ldw, cout, stride, relu_in, bias, act, res0, 0, res1,
+                       nullptr, 0, 0, out, ws, ws_floats, slices, nullptr, 0, 0, st);
+}
+
+int mde_op_linear_ws(const void* a, int lda, const void* wt, int ldw, int m, int n, int k, const float* bias, int act,
+                     void* out, int ldo, float* ws, size_t ws_floats, int* slices, void* st) {
+  return linear_store("linear_ws", a, lda, wt, ldw, m, n, k, bias, act, nullptr, 0, 0, nullptr, out, ldo, ws,
+                      ws_floats, slices, nullptr, 0, 0, st);
+}
+
+int mde_op_conv3x3_up(const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt, int ldw,
+                      int cout, const float* bias, int act, void* out, void* st) {
+  if (!in || !wt || !out) return fail(MDE_ERR_ARG, "null argument");
+  GemmParams g = gemm_conv3_up((const h16*)in, batch, sh, sw, cin, uh, uw, (const h16*)wt, ldw, cout);
+  g.bias = bias;
+  g.act = act;
+  g.out16 = (h16*)out;
+  g.ldo = cout;
+  OP_RET(launch_gemm(g, (hipStream_t)st), "conv3x3_up");
+}
+
+namespace {
+// mde_op_conv_transpose_ld and its subset mde_op_conv_transpose (ldo = cout)
+int conv_transpose(const char* what, const void* in, int batch, int h, int w, int cin, const void* wt, int ldw,
+                   int cout, int stride, const float* bias, void* out, int ldo, void* st) {
+  if (!in || !wt || !bias || !out) return fail(MDE_ERR_ARG, "null argument");
+  GemmParams g = gemm_convt((const h16*)in, batch, h, w, cin, (const h16*)wt, ldw, cout, stride, (h16*)out, ldo);
+  g.bias = bias;
+  return op_status(launch_gemm(g, (hipStream_t)st), what);
+}
+}  // namespace
+
+int mde_op_conv_transpose(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout,
+                          int stride, const float* bias, void* out, void* st) {
+  return conv_transpose("conv_transpose", in, batch, h, w, cin, wt, ldw, cout, stride, bias, out, cout, st);
+}
+
+int mde_op_resize_bilinear(const void* in, int batch, int ih, int iw, int c, int oh, int ow, void* out, void* st) {
+  if (!in || !out) return fail(MDE_ERR_ARG, "null argument");
+  OP_RET(launch_resize((const h16*)in, (h16*)out, batch, ih, iw, c, oh, ow, (hipStream_t)st), "resize_bilinear");
+}
+
+namespace {
+// mde_op_depth_head_pe and its subset mde_op_depth_head (no hpe)
+int depth_head(const char* what, const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt,
+               int ldw, const float* bias, const float* w2, float b2, int metric, float max_depth, const void* hpe,
+               int hpe_pix, float* out, void* st) {
+  if (!in || !wt || !bias || !w2 || !out) return fail(MDE_ERR_ARG, "null argument");
+  if (hpe && hpe_pix < 1) return fail(MDE_ERR_ARG, "hpe needs hpe_pix >= 1");
+  GemmParams g = gemm_conv3_up((const h16*)in, batch, sh, sw, cin, uh, uw, (const h16*)wt, ldw, 32);
+  g.bias = bias;
+  set_head(g, w2, b2, metric, max_depth, (const h16*)hpe, hpe ? hpe_pix : 0, out);
+  return op_status(launch_gemm(g, (hipStream_t)st), what);
+}
+}  // namespace
+
+int mde_op_depth_head(const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt, int ldw,
+                      const float* bias, const float* w2, float b2, int metric, float max_depth, float* out,
+                      void* st) {
+  return depth_head("depth_head", in, batch, sh, sw, cin, uh, uw, wt, ldw, bias, w2, b2, metric, max_depth, nullptr, 0,
+                    out, st);
+}
+
+// ---- the GemmParams options only the engine graphs set, one wrapper each ----
+// (no kernel code and no policy here: launch_gemm picks the route as it does
+// for the engines; tests/test_gpu_ops_engine_paths.py)
+int mde_op_linear_res(const void* a, int lda, const void* wt, int ldw, int m, int n, int k, const float* bias, int act,
+                      const void* res0, int res0_rows, int res0_relu, const void* res1, void* out, int ldo, float* ws,
+                      size_t ws_floats, int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats, void* st) {
+  return linear_store("linear_res", a, lda, wt, ldw, m, n, k, bias, act, res0, res0_rows, res0_relu, res1, out, ldo,
+                      ws, ws_floats, slices, tile_cnt, tile_cnt_cap, slot_floats, st);
+}
+
+int mde_op_conv3x3_res(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout, int stride,
+                       int relu_in, const float* bias, int act, const void* res0, int res0_relu, const void* res1,
+                       const void* res1_up, int res1_uh, int res1_uw, void* out, float* ws, size_t ws_floats,
+                       int* slices, int* tile_cnt, int tile_cnt_cap, size_t slot_floats, void* st) {
+  return conv3x3_store("conv3x3_res", in, batch, h, w, cin, wt, ldw, cout, stride, relu_in, bias, act, res0, res0_relu,
+                       res1, res1_up, res1_uh, res1_uw, out, ws, ws_floats, slices, tile_cnt, tile_cnt_cap,
+                       slot_floats, st);
+}
+
+int mde_op_linear_lnfold_tok(const void* x, const float* ln_partials, float eps, const void* wg, int ldw,
+                             const float* c1, const float* c2, int seqs, int tokens, int n, int k, int act, void* out,
+                             int ldo, void* st) {
+  if (!x || !ln_partials || !wg || !c1 || !c2 || !out) return fail(MDE_ERR_ARG, "null argument");
+  if (k & 31) return fail(MDE_ERR_ARG, "k % 32 != 0");
+  if (seqs < 1 || tokens < 2) return fail(MDE_ERR_ARG, "seqs >= 1 and tokens >= 2 (a cls row and at least one more)");
+  return linear_lnfold("linear_lnfold_tok", x, ln_partials, eps, wg, ldw, c1, c2, seqs * (tokens - 1), n, k, act, out,
+                       ldo, seqs * tokens, tokens, st);
+}
+
+int mde_op_depth_head_pe(const void* in, int batch, int sh, int sw, int cin, int uh, int uw, const void* wt, int ldw,
+                         const float* bias, const float* w2, float b2, int metric, float max_depth, const void* hpe,
+                         int hpe_pix, float* out, void* st) {
+  return depth_head("depth_head_pe", in, batch, sh, sw, cin, uh, uw, wt, ldw, bias, w2, b2, metric, max_depth, hpe,
+                    hpe_pix, out, st);
+}
+
+int mde_op_conv_transpose_ld(const void* in, int batch, int h, int w, int cin, const void* wt, int ldw, int cout,
+                             int stride, const float* bias, void* out, int ldo, void* st) {
+  return conv_transpose("conv_transpose_ld", in, batch, h, w, cin, wt, ldw, cout, stride, bias, out, ldo, st);
+}
+
+int mde_op_linear_residual_split(const void* a, int lda, const void* wt, int ldw, int m, int n, int k,
+                                 const float* bias, const float* ls, float* x32, void* xh, int ldx, float* ln_partials,
+                                 int splitk, float* ws, size_t ws_floats, int* tile_cnt, int tile_cnt_cap,
+                                 size_t slot_floats, void* st) {
+  if (!a || !wt || !bias || !ls || (!x32 == !xh) || (!ws && ws_floats))
+    return fail(MDE_ERR_ARG, "null argument (one of x32 / xh)");
+  if (ln_partials && (!xh || (n & 31))) return fail(MDE_ERR_ARG, "ln_partials need xh and n % 32 == 0");
+  if (m < 0 || n < 0 || splitk < 0) return fail(MDE_ERR_ARG, "negative size");
+  // the 128^2 route cuts K into 4 slices whatever splitk says
+  if (splitk > 1 && (!ws || ws_floats / (size_t)(splitk > 4 ? splitk : 4) < (size_t)m * (size_t)n))
+    return fail(MDE_ERR_ARG, "ws must hold max(splitk, 4) * m * n floats");
+  if (const char* why = fused_split_error(ws, ws_floats, tile_cnt, tile_cnt_cap, slot_floats, m, n))
+    return fail(MDE_ERR_ARG, why);
+  GemmParams g = gemm_dense((const h16*)a, lda, (const h16*)wt, ldw, m, n, k);
+  set_resid(g, bias, ls, x32, (h16*)xh, ldx);
+  if (ln_partials) set_ln_producer(g, ln_partials, m);
+  if (splitk > 1) set_resid_splitk(g, ws, splitk, slot_floats, tile_cnt, tile_cnt_cap);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual_split");
+}
+
+}  // extern "C"

@@ -34,8 +34,6 @@ namespace mde {
 
 namespace {
 
-constexpr float kQScale = 0.125f * 1.4426950408889634f;  // dh^-0.5 * log2(e): scores in log2 units
-
 bool dims_are(const DevTensor* t, std::initializer_list<int> d) {
   if (!t || t->ndim != (int)d.size()) return false;
   int i = 0;
@@ -127,11 +125,7 @@ std::string setup_vggt(mde_engine* e) {
 size_t plan_arena_vggt(const mde_engine& e, int B, VGBuf* b, uint8_t* base) {
   ArenaPlan a(base);
   const size_t n = (size_t)B * e.S;  // frames in the batch
-  const size_t T = e.T, D = e.D, F = e.F, np = e.np;
-  const int* oc = e.cfg.out_channels;
-  const size_t s1 = (size_t)(4 * e.ph) * (4 * e.pw), s2 = (size_t)(2 * e.ph) * (2 * e.pw), s3 = np,
-               s4 = (size_t)e.h4 * e.w4;
-  const size_t s0 = (size_t)(8 * e.ph) * (8 * e.pw);
+  const size_t T = e.T, D = e.D, np = e.np;
   VGBuf t{};
   t.P = a.h(n * np * 672);
   t.X = a.f(n * T * D);
@@ -152,20 +146,7 @@ size_t plan_arena_vggt(const mde_engine& e, int B, VGBuf* b, uint8_t* base) {
     t.Vg = t.Vt;
   }
   t.tap = a.h(n * np * 2 * D);
-  for (int i = 0; i < 4; ++i) t.pj[i] = a.h(n * np * oc[i]);
-  t.l1 = a.h(n * s1 * e.c1p);
-  t.l2 = a.h(n * s2 * oc[1]);
-  t.l4 = a.h(n * s4 * oc[3]);
-  const size_t ss[4] = {s1, s2, s3, s4};
-  for (int i = 0; i < 4; ++i) t.rn[i] = a.h(n * ss[i] * F);
-  t.tb = a.h(n * s1 * F);
-  t.sb = a.h(n * s1 * F);
-  t.ub = a.h(n * s1 * F);
-  t.vb = a.h(n * s1 * F);
-  t.p4 = a.h(n * s3 * F);
-  t.p3 = a.h(n * s2 * F);
-  t.p2 = a.h(n * s1 * F);
-  t.c1 = a.h(n * s0 * (F / 2));
+  t.m = plan_dpt_maps(a, n, e);
   t.ws_rows = n * T <= 4096 ? n * T : 0;
   t.ws = t.ws_rows ? a.f(fc2_ws_floats(t.ws_rows, D)) : nullptr;
   t.sws = a.f(kSplitWsAlloc);
@@ -173,117 +154,55 @@ size_t plan_arena_vggt(const mde_engine& e, int B, VGBuf* b, uint8_t* base) {
   return a.off;
 }
 
-// One transformer block over `seqs` sequences of T tokens (the residual
-// stream c.v.X, seqs * T rows).  qk: aggregator block (q/k LayerNorm + RoPE,
-// the q scale applied after them); else a DINOv2 block (q pre-scaled by the
-// QKV epilogue).
-void Runner::vggt_block(const std::string& p, float eps, bool qk, int seqs, int T, int Tpad, h16* Q, h16* K, h16* Vt) {
-  mde_engine& e = *c.e;
-  VGBuf& v = c.v;
-  const int D = e.D, rows = seqs * T, mlp = e.cfg.mlp_hidden;
-  step((p + "norm1").c_str(), [&] {
-    return launch_layernorm(v.X, v.Hn, w32(p + "ln1.g"), w32(p + "ln1.b"), rows, D, eps, T, 0, st);
-  });
-  {
-    GemmParams g = dense(v.Hn, D, p + "qkv.w", rows, 3 * D, D);
-    g.emode = E_QKV;
-    g.bias = w32(p + "qkv.b");
-    g.q = Q;
-    g.k = K;
-    g.vt = Vt;
-    g.T = T;
-    g.Tpad = Tpad;
-    g.heads = e.H;
-    g.qscale = qk ? 1.f : kQScale;
-    gemm((p + "qkv").c_str(), g);
-  }
-  if (qk) {
-    RopeGeom geo;
-    geo.T = T;
-    geo.Tpad = Tpad;
-    geo.P = e.T;
-    geo.npre = e.npre;
-    geo.gw = e.pw;
-    geo.qscale = kQScale;
-    geo.eps = eps;
-    step((p + "qk_rope").c_str(), [&] {
-      return launch_qk_norm_rope(Q, K, w32(p + "qn.g"), w32(p + "qn.b"), w32(p + "kn.g"), w32(p + "kn.b"),
-                                 w32("rope.cos"), w32("rope.sin"), seqs * e.H, geo, st);
-    });
-  }
-  step((p + "attn").c_str(), [&] { return launch_attention(Q, K, Vt, v.O, seqs, e.H, T, Tpad, D, st); });
-  {
-    GemmParams g = dense(v.O, D, p + "proj.w", rows, D, D);
-    g.emode = E_RESID;
-    g.bias = w32(p + "proj.b");
-    g.ls = w32(p + "ls1");
-    g.x32 = v.X;
-    g.ldo = D;
-    gemm((p + "proj").c_str(), g);
-  }
-  step((p + "norm2").c_str(), [&] {
-    return launch_layernorm(v.X, v.Hn, w32(p + "ln2.g"), w32(p + "ln2.b"), rows, D, eps, T, 0, st);
-  });
-  {
-    GemmParams g = dense(v.Hn, D, p + "fc1.w", rows, mlp, D);
-    g.emode = E_STORE;
-    g.bias = w32(p + "fc1.b");
-    g.act = ACT_GELU;
-    g.out16 = v.Mh;
-    g.ldo = mlp;
-    gemm((p + "fc1").c_str(), g);
-  }
-  {
-    GemmParams g = dense(v.Mh, mlp, p + "fc2.w", rows, D, mlp);
-    g.emode = E_RESID;
-    g.bias = w32(p + "fc2.b");
-    g.ls = w32(p + "ls2");
-    g.x32 = v.X;
-    g.ldo = D;
-    // small batch: split fc2's K = 4D loop (as the DA-V2 fc2, engine.hip);
-    // B = 1, S = 1: 352 64^2 tiles x 2 slices
-    const long long t64 = (long long)((rows + 63) / 64) * ((D + 63) / 64);
-    if (v.ws && (size_t)rows <= v.ws_rows && t64 < 512 && mlp >= 1024 && knob(KNOB_SPLITK)) {
-      g.partial = v.ws;
-      g.splitk = t64 < 256 ? 4 : 2;
-      g.slot_cap = fc2_ws_floats(rows, D);
-      g.tile_cnt = split_counters(v.sws);
-      g.tile_cnt_cap = kTileCnt;
-    }
-    gemm((p + "fc2").c_str(), g);
-  }
-}
-
-// FeatureFusionBlock with in-place-ReLU residual units (the skips add
-// relu(x)); out_conv (1x1) before the resize, as dav2_fusion.
-void Runner::vggt_fusion(int r, const h16* x0, const h16* x1, int n, int h, int w, h16* dst, int oh, int ow) {
-  const std::string p = "rf" + std::to_string(r);
-  const int F = c.e->F;
-  VGBuf& v = c.v;
-  const h16* s = x0;
-  if (x1) {
-    rcu(p + ".rcu1", x1, x0, v.sb, v.tb, n, h, w, F, true);
-    s = v.sb;
-  }
-  rcu(p + ".rcu2", s, nullptr, v.ub, v.tb, n, h, w, F, true);
-  GemmParams g = dense(v.ub, F, p + ".out.w", n * h * w, F, F);
-  g.emode = E_STORE;
-  g.bias = w32(p + ".out.b");
-  g.out16 = v.vb;
-  g.ldo = F;
-  gemm((p + ".out").c_str(), g);
-  if (dst) step((p + ".resize").c_str(), [&] { return launch_resize(v.vb, dst, n, h, w, F, oh, ow, st); });
-}
-
 hipError_t Runner::forward_vggt(int B, const float* img, float* out) {
   mde_engine& e = *c.e;
   const PackConfig& cf = e.cfg;
   VGBuf& v = c.v;
   const int n = B * e.S;  // frames
-  const int D = e.D, T = e.T, np = e.np, F = e.F;
+  const int D = e.D, T = e.T, np = e.np;
   const int* oc = cf.out_channels;
   char nm[64];
   split_ws = v.sws;
+
+  // One transformer block over `seqs` sequences of T tokens (the residual
+  // stream v.X, seqs * T rows).  qk: aggregator block (q/k LayerNorm + RoPE,
+  // the q scale applied after them); else a DINOv2 block (q pre-scaled by the
+  // QKV epilogue).
+  auto block = [&](const std::string& p, float eps, bool qk, int seqs, int T, int Tpad, h16* Q, h16* K, h16* Vt) {
+    VitBlock blk;
+    blk.w = blk.name = p;
+    blk.seqs = seqs;
+    blk.T = T;
+    blk.Tpad = Tpad;
+    blk.eps = eps;
+    blk.qscale = qk ? 1.f : kQScale;
+    blk.X = v.X;
+    blk.Hn = v.Hn;
+    blk.Q = Q;
+    blk.K = K;
+    blk.Vt = Vt;
+    blk.O = v.O;
+    blk.Mh = v.Mh;
+    blk.ws = v.ws;
+    blk.ws_rows = v.ws_rows;
+    blk.counters = split_counters(v.sws);
+    if (qk)
+      blk.after_qkv = [&] {
+        RopeGeom geo;
+        geo.T = T;
+        geo.Tpad = Tpad;
+        geo.P = e.T;
+        geo.npre = e.npre;
+        geo.gw = e.pw;
+        geo.qscale = kQScale;
+        geo.eps = eps;
+        step((p + "qk_rope").c_str(), [&] {
+          return launch_qk_norm_rope(Q, K, w32(p + "qn.g"), w32(p + "qn.b"), w32(p + "kn.g"), w32(p + "kn.b"),
+                                     w32("rope.cos"), w32("rope.sin"), seqs * e.H, geo, st);
+        });
+      };
+    vit_block(blk);
+  };
 
   // ---- DINOv2-L/14-reg patch embedding over all frames ----
   step("patch_prep", [&] {
@@ -303,7 +222,7 @@ hipError_t Runner::forward_vggt(int B, const float* img, float* out) {
     gemm("patch_embed", g);
   }
   for (int i = 0; i < cf.depth; ++i)
-    vggt_block("db" + std::to_string(i) + ".", cf.ln_eps, false, n, T, e.Tpad, v.Q, v.K, v.Vt);
+    block("db" + std::to_string(i) + ".", cf.ln_eps, false, n, T, e.Tpad, v.Q, v.K, v.Vt);
   step("dino.norm", [&] {
     return launch_rows_layernorm(v.X, w32("norm.g"), w32("norm.b"), n, T, e.npre, D, cf.ln_eps, st);
   });
@@ -311,7 +230,7 @@ hipError_t Runner::forward_vggt(int B, const float* img, float* out) {
   step("agg.prefix", [&] { return launch_prefix_rows(v.X, w32("pre.agg"), n, T, e.npre, D, e.S, 2, st); });
   int tap = 0;
   for (int i = 0; i < cf.aa_depth; ++i) {
-    vggt_block("fb" + std::to_string(i) + ".", cf.agg_eps, true, n, T, e.Tpad, v.Q, v.K, v.Vt);
+    block("fb" + std::to_string(i) + ".", cf.agg_eps, true, n, T, e.Tpad, v.Q, v.K, v.Vt);
     const bool tapped = tap < 4 && cf.taps[tap] == i;
     if (tapped) {
       snprintf(nm, sizeof nm, "tap%d.frame_copy", tap);
@@ -319,7 +238,7 @@ hipError_t Runner::forward_vggt(int B, const float* img, float* out) {
         return hipMemcpyAsync(v.Xf, v.X, (size_t)n * T * D * sizeof(float), hipMemcpyDeviceToDevice, st);
       });
     }
-    vggt_block("gb" + std::to_string(i) + ".", cf.agg_eps, true, B, e.Tg, e.Tgpad, v.Qg, v.Kg, v.Vg);
+    block("gb" + std::to_string(i) + ".", cf.agg_eps, true, B, e.Tg, e.Tgpad, v.Qg, v.Kg, v.Vg);
     if (!tapped) continue;
     // depth-head tap: LN over cat(frame, global) patch tokens -> 1x1 projection + UV embedding
     snprintf(nm, sizeof nm, "tap%d.norm", tap);
@@ -330,7 +249,7 @@ hipError_t Runner::forward_vggt(int B, const float* img, float* out) {
     GemmParams g = dense(v.tap, 2 * D, "proj" + std::to_string(tap) + ".w", n * np, oc[tap], 2 * D);
     g.emode = E_STORE;
     g.bias = w32("proj" + std::to_string(tap) + ".b");
-    g.out16 = v.pj[tap];
+    g.out16 = v.m.pj[tap];
     g.ldo = oc[tap];
     g.res0 = w16("pe" + std::to_string(tap));
     g.res0_rows = np;
@@ -340,106 +259,16 @@ hipError_t Runner::forward_vggt(int B, const float* img, float* out) {
   }
   if (tap != 4) return hipErrorInvalidValue;
 
-  // ---- DPT decoder (as forward_dav2, over the n frames) ----
-  {
-    GemmParams g = dense(v.pj[0], oc[0], "rs0.w", n * np, 16 * oc[0], oc[0]);
-    g.emode = E_CONVT;
-    g.bias = w32("rs0.b");
-    g.out16 = v.l1;
-    g.s = 4;
-    g.cout = oc[0];
-    g.ldo = e.c1p;
-    g.ih = e.ph;
-    g.iw = e.pw;
-    gemm("reassemble0.convT4", g);
-  }
-  {
-    GemmParams g = dense(v.pj[1], oc[1], "rs1.w", n * np, 4 * oc[1], oc[1]);
-    g.emode = E_CONVT;
-    g.bias = w32("rs1.b");
-    g.out16 = v.l2;
-    g.s = 2;
-    g.cout = oc[1];
-    g.ldo = oc[1];
-    g.ih = e.ph;
-    g.iw = e.pw;
-    gemm("reassemble1.convT2", g);
-  }
-  {
-    GemmParams g = conv(v.pj[3], n, e.ph, e.pw, oc[3], "rs3.w", oc[3], 2);
-    g.bias = w32("rs3.b");
-    g.out16 = v.l4;
-    gemm("reassemble3.conv_s2", g);
-  }
-  const int hs[4] = {4 * e.ph, 2 * e.ph, e.ph, e.h4};
-  const int ws[4] = {4 * e.pw, 2 * e.pw, e.pw, e.w4};
-  const h16* lay[4] = {v.l1, v.l2, v.pj[2], v.l4};
-  const int cin[4] = {e.c1p, oc[1], oc[2], oc[3]};
-  for (int i = 0; i < 4; ++i) {
-    GemmParams g = conv(lay[i], n, hs[i], ws[i], cin[i], "rn" + std::to_string(i + 1) + ".w", F, 1);
-    g.out16 = v.rn[i];
-    snprintf(nm, sizeof nm, "layer%d_rn", i + 1);
-    gemm(nm, g);
-  }
-  vggt_fusion(4, v.rn[3], nullptr, n, hs[3], ws[3], v.p4, hs[2], ws[2]);
-  vggt_fusion(3, v.p4, v.rn[2], n, hs[2], ws[2], v.p3, hs[1], ws[1]);
-  vggt_fusion(2, v.p3, v.rn[1], n, hs[1], ws[1], v.p2, hs[0], ws[0]);
-  vggt_fusion(1, v.p2, v.rn[0], n, hs[0], ws[0], nullptr, 0, 0);  // 1x1 result in vb at hs[0] x ws[0]
-  // ---- head ----
-  const int H1 = 2 * hs[0], W1 = 2 * ws[0];
-  {
-    GemmParams g;
-    g.amode = A_CONV3_UP;
-    g.emode = E_STORE;
-    g.A = v.vb;
-    g.cb = n;
-    g.ch = hs[0];
-    g.cw = ws[0];
-    g.cc = F;
-    g.uh = H1;
-    g.uw = W1;
-    g.oh = H1;
-    g.ow = W1;
-    g.stride = 1;
-    g.W = w16("head.c1.w");
-    g.ldw = ldw("head.c1.w");
-    g.M = n * H1 * W1;
-    g.N = F / 2;
-    g.K = 9 * F;
-    g.bias = w32("head.c1.b");
-    g.out16 = v.c1;
-    g.ldo = F / 2;
-    gemm("head.output_conv1", g);
-  }
-  {
-    const int OH = cf.img_h, OW = cf.img_w;
-    GemmParams g;
-    g.amode = A_CONV3_UP;
-    g.emode = E_HEAD;
-    g.A = v.c1;
-    g.cb = n;
-    g.ch = H1;
-    g.cw = W1;
-    g.cc = F / 2;
-    g.uh = OH;
-    g.uw = OW;
-    g.oh = OH;
-    g.ow = OW;
-    g.stride = 1;
-    g.W = w16("head.c2.w");
-    g.ldw = ldw("head.c2.w");
-    g.M = n * OH * OW;
-    g.N = cf.head_hidden;
-    g.K = 9 * (F / 2);
-    g.bias = w32("head.c2.b");
-    g.hpe = w16("head.pe");
-    g.hpe_pix = OH * OW;
-    g.w2 = w32("head.c3.w");
-    g.b2 = e.head_b2;
-    g.head_metric = 2;  // depth = exp(channel 0) (upstream activate_head "exp")
-    g.out32 = out;
-    gemm("head.output_conv2", g);
-  }
+  // ---- DPT decoder (the DA-V2 steps, over the n frames): the resize layers,
+  // then the four layerN_rn, fusion with in-place-ReLU residual units ----
+  dpt_resize_layer(v.m, n, 0);
+  dpt_resize_layer(v.m, n, 1);
+  dpt_resize_layer(v.m, n, 3);
+  for (int i = 0; i < 4; ++i) dpt_layer_rn(v.m, n, i);
+  for (int r = 4; r >= 1; --r) dpt_fusion(v.m, n, r, true, false);
+  // ---- head: depth = exp(channel 0) (upstream activate_head "exp"; max_depth unused) ----
+  dpt_head_conv1(v.m, n);
+  dpt_head_conv2(v.m, n, 2, 1.f, w16("head.pe"), cf.img_h * cf.img_w, out);
   return err;
 }
 

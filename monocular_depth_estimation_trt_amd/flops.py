@@ -7,7 +7,8 @@ engine runs it before the resize (4x fewer MACs, exact by linearity).  These
 are the numbers roofline fractions are quoted against (ViT-S
 115.27 GFLOP/img, ViT-L 1304.22 GFLOP/img at 518^2).
 
-Layer names match the engine's profiler names (csrc/engine.hip Runner).
+Layer names match the engine's profiler names (csrc/engine.hip: Runner::forward_dav2 and the
+shared vit_block / dpt_* steps; pinned by tests/golden/layer_schedule.json).
 """
 
 from __future__ import annotations

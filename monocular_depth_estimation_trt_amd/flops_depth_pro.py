@@ -7,7 +7,8 @@ two layers it is in the reference even though the engine runs them as one
 folded ConvT (half the MACs), and the FOV neck Linear is counted on all 577
 tokens (cls included) as the reference applies it.
 
-Layer names match the engine's profiler names (csrc/depth_pro.hip Runner).
+Layer names match the engine's profiler names (csrc/depth_pro.hip Runner; the encoder
+blocks are csrc/engine.hip Runner::vit_block).
 """
 
 from __future__ import annotations

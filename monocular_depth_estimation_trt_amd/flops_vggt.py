@@ -9,7 +9,8 @@ UV embedding convolution the packer folds into a table is not counted at all
 (it is input-independent).  Global attention is counted over the whole
 S * T sequence of each batch item.
 
-Layer names match the engine's profiler names (csrc/vggt.hip Runner).
+Layer names match the engine's profiler names (csrc/vggt.hip Runner::forward_vggt; the
+block and DPT decoder steps it shares with DA-V2 are in csrc/engine.hip).
 """
 
 from __future__ import annotations

@@ -296,7 +296,7 @@ def test_fc2_splitk_matches_unsplit(gpu, encoder, size):
 @pytest.mark.parametrize("encoder,size,B", [("vits", 518, 1), ("vits", 518, 8), ("vitl", 518, 1), ("vits", 98, 2),
                                             ("vitb", 126, 1)])
 def test_resize_fold_bit_exact(gpu, encoder, size, B):
-    """Switch "resize_fold" (engine.hip dav2_fusion, GemmParams::res1_up): the
+    """Switch "resize_fold" (engine.hip dpt_fusion, GemmParams::res1_up): the
     fusion blocks' x2 resize is not launched; the next block's rcu1 second conv
     reads the 1x1 output through the same align_corners blend (mde_device.h
     upsample8) in its epilogue -- the direct conv -- or writes it into the

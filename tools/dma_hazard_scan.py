@@ -130,7 +130,7 @@ def classify(hits):
 
 def disassemble(obj: str, require: bool = True) -> str:
     """Device (gfx950) disassembly of a hipcc object or shared library;
-    `require=False` for objects that may hold host code only (engine.hip)."""
+    `require=False` for objects that may hold host code only (engine.hip, ops_abi.hip)."""
     d = tempfile.mkdtemp()
     try:
         c = os.path.join(d, os.path.basename(obj))
