@@ -36,12 +36,16 @@ def GiB(val):
     return val * 1 << 30
 
 
+def _synthetic_fields(src: str, *defaults):
+    """The ':'-separated fields after "synthetic" of a synthetic source; an
+    absent or empty field takes its default (the seed, last, as int)."""
+    parts = src.split(":")[1:]
+    out = [parts[k] if len(parts) > k and parts[k] else d for k, d in enumerate(defaults)]
+    return (*out[:-1], int(out[-1]))
+
+
 def _parse_synthetic(src: str):
-    parts = src.split(":")
-    enc = parts[1] if len(parts) > 1 and parts[1] else "vits"
-    dtype = parts[2] if len(parts) > 2 and parts[2] else "metric"
-    seed = int(parts[3]) if len(parts) > 3 and parts[3] else 1234
-    return enc, dtype, seed
+    return _synthetic_fields(src, "vits", "metric", 1234)
 
 
 def _source_digest(src: str) -> str:
@@ -230,14 +234,14 @@ def get_engine(onnx_file_path, engine_file_path="", precision="fp32", dynamic_in
         if not present:
             raise FileNotFoundError(f"[MDET] source {src} not found.")
         if is_depth_pro_source(src):
-            parts = src.split(":")
-            cfg = weights_depth_pro.depth_pro_config(parts[2] if len(parts) > 2 and parts[2] else "dinov2l16_384")
-            sd = weights_depth_pro.synthetic_state_dict(cfg, int(parts[3]) if len(parts) > 3 and parts[3] else 4321)
+            _, preset, seed = _synthetic_fields(src, "depth_pro", "dinov2l16_384", 4321)
+            cfg = weights_depth_pro.depth_pro_config(preset)
+            sd = weights_depth_pro.synthetic_state_dict(cfg, seed)
             return pack_depth_pro.pack_bytes(sd, cfg)
         if is_vggt_source(src):
-            parts = src.split(":")
-            cfg = weights_vggt.vggt_config(parts[2] if len(parts) > 2 and parts[2] else "vggt_1b")
-            sd = weights_vggt.synthetic_state_dict(cfg, int(parts[3]) if len(parts) > 3 and parts[3] else 2468)
+            _, preset, seed = _synthetic_fields(src, "vggt", "vggt_1b", 2468)
+            cfg = weights_vggt.vggt_config(preset)
+            sd = weights_vggt.synthetic_state_dict(cfg, seed)
             return build_vggt(sd, cfg)
         if not src.startswith("synthetic:"):
             sd = load_checkpoint(src)

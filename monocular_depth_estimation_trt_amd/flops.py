@@ -17,47 +17,48 @@ from collections import OrderedDict
 from typing import Dict
 
 
-def layer_flops(cfg: dict, img_h: int = 518, img_w: int = 518, batch: int = 1) -> "OrderedDict[str, float]":
-    P = cfg["patch"]
-    ph, pw = img_h // P, img_w // P
+def block_flops(o, pfx: str, seqs: int, L: int, D: int, M4: int) -> None:
+    """One ViT block over `seqs` sequences of `L` tokens, as `pfx`.qkv/.attn/.proj/.fc1/.fc2."""
+    o[pfx + ".qkv"] = 2.0 * seqs * L * 3 * D * D
+    o[pfx + ".attn"] = 4.0 * seqs * L * L * D
+    o[pfx + ".proj"] = 2.0 * seqs * L * D * D
+    o[pfx + ".fc1"] = 2.0 * seqs * L * M4 * D
+    o[pfx + ".fc2"] = 2.0 * seqs * L * D * M4
+
+
+def dpt_flops(o, cfg: dict, ph: int, pw: int, img_px: int, n: int, in_dim: int, out_dim: int = 1) -> None:
+    """The DPT decoder (reassemble, layerN_rn, refinenets, head) on `n` frames
+    of a ph x pw token grid: projections from `in_dim` channels, the head at
+    `img_px` pixels with `out_dim` 1x1 outputs."""
+    F, oc = cfg["features"], cfg["out_channels"]
     npch = ph * pw
-    T = npch + 1
-    D, F = cfg["embed_dim"], cfg["features"]
-    oc = cfg["out_channels"]
-    M4 = cfg["mlp_hidden"]
-    h4, w4 = (ph + 1) // 2, (pw + 1) // 2
-    s = [(4 * ph) * (4 * pw), (2 * ph) * (2 * pw), npch, h4 * w4]
-    o: "OrderedDict[str, float]" = OrderedDict()
-    o["patch_embed"] = 2.0 * npch * D * 3 * P * P
-    for i in range(cfg["depth"]):
-        o[f"block{i}.qkv"] = 2.0 * T * 3 * D * D
-        o[f"block{i}.attn"] = 4.0 * T * T * D
-        o[f"block{i}.proj"] = 2.0 * T * D * D
-        o[f"block{i}.fc1"] = 2.0 * T * M4 * D
-        o[f"block{i}.fc2"] = 2.0 * T * D * M4
+    s = [(4 * ph) * (4 * pw), (2 * ph) * (2 * pw), npch, ((ph + 1) // 2) * ((pw + 1) // 2)]
     for i in range(4):
-        o[f"reassemble{i}.project"] = 2.0 * npch * D * oc[i]
-    o["reassemble0.convT4"] = 2.0 * npch * oc[0] * oc[0] * 16
-    o["reassemble1.convT2"] = 2.0 * npch * oc[1] * oc[1] * 4
-    o["reassemble3.conv_s2"] = 2.0 * s[3] * oc[3] * oc[3] * 9
+        o[f"reassemble{i}.project"] = 2.0 * n * npch * in_dim * oc[i]
+    o["reassemble0.convT4"] = 2.0 * n * npch * oc[0] * oc[0] * 16
+    o["reassemble1.convT2"] = 2.0 * n * npch * oc[1] * oc[1] * 4
+    o["reassemble3.conv_s2"] = 2.0 * n * s[3] * oc[3] * oc[3] * 9
     for i in range(4):
-        o[f"layer{i + 1}_rn"] = 2.0 * s[i] * F * oc[i] * 9
+        o[f"layer{i + 1}_rn"] = 2.0 * n * s[i] * F * oc[i] * 9
     # refinenet r works at scale index r-1; out_conv after the resize
-    scale = {4: 3, 3: 2, 2: 1, 1: 0}
     target = {4: s[2], 3: s[1], 2: s[0], 1: 4 * s[0]}
     for r in (4, 3, 2, 1):
-        px = s[scale[r]]
-        units = (2,) if r == 4 else (1, 2)
-        for u in units:
-            o[f"rf{r}.rcu{u}.c1"] = 2.0 * px * F * F * 9
-            o[f"rf{r}.rcu{u}.c2"] = 2.0 * px * F * F * 9
-        o[f"rf{r}.out"] = 2.0 * target[r] * F * F
-    H1 = (8 * ph) * (8 * pw)
-    o["head.output_conv1"] = 2.0 * H1 * (F // 2) * F * 9
-    o["head.output_conv2"] = 2.0 * img_h * img_w * (cfg["head_hidden"] * (F // 2) * 9 + cfg["head_hidden"])
-    if batch != 1:
-        for k in o:
-            o[k] *= batch
+        for u in ((2,) if r == 4 else (1, 2)):
+            o[f"rf{r}.rcu{u}.c1"] = 2.0 * n * s[r - 1] * F * F * 9
+            o[f"rf{r}.rcu{u}.c2"] = 2.0 * n * s[r - 1] * F * F * 9
+        o[f"rf{r}.out"] = 2.0 * n * target[r] * F * F
+    o["head.output_conv1"] = 2.0 * n * (8 * ph) * (8 * pw) * (F // 2) * F * 9
+    o["head.output_conv2"] = 2.0 * n * img_px * (cfg["head_hidden"] * (F // 2) * 9 + cfg["head_hidden"] * out_dim)
+
+
+def layer_flops(cfg: dict, img_h: int = 518, img_w: int = 518, batch: int = 1) -> "OrderedDict[str, float]":
+    P, D = cfg["patch"], cfg["embed_dim"]
+    ph, pw = img_h // P, img_w // P
+    o: "OrderedDict[str, float]" = OrderedDict()
+    o["patch_embed"] = 2.0 * batch * ph * pw * D * 3 * P * P
+    for i in range(cfg["depth"]):
+        block_flops(o, f"block{i}", batch, ph * pw + 1, D, cfg["mlp_hidden"])
+    dpt_flops(o, cfg, ph, pw, img_h * img_w, batch, D)
     return o
 
 
@@ -84,9 +85,14 @@ def layer_class(name: str) -> str:
     return name
 
 
-def class_flops(cfg: dict, img_h: int = 518, img_w: int = 518, batch: int = 1) -> Dict[str, float]:
+def sum_classes(layers: Dict[str, float], layer_class) -> Dict[str, float]:
+    """A layer_flops table summed per layer_class, in first-seen order."""
     out: Dict[str, float] = {}
-    for k, v in layer_flops(cfg, img_h, img_w, batch).items():
+    for k, v in layers.items():
         c = layer_class(k)
         out[c] = out.get(c, 0.0) + v
     return out
+
+
+def class_flops(cfg: dict, img_h: int = 518, img_w: int = 518, batch: int = 1) -> Dict[str, float]:
+    return sum_classes(layer_flops(cfg, img_h, img_w, batch), layer_class)

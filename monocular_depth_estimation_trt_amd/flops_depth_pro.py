@@ -16,12 +16,13 @@ from __future__ import annotations
 from collections import OrderedDict
 from typing import Dict
 
+from .flops import block_flops, sum_classes
+
 
 def layer_flops(cfg: dict, batch: int = 1) -> "OrderedDict[str, float]":
     D, F, P = cfg["embed_dim"], cfg["fusion"], cfg["patch"]
     G = cfg["vit_size"] // P
     GG, T = G * G, G * G + 1
-    M4 = cfg["mlp_hidden"]
     sd0, sd1, sd2 = cfg["scaled_dims"]
     id0, id1 = cfg["inter_dims"]
     S = cfg["img"]
@@ -30,11 +31,7 @@ def layer_flops(cfg: dict, batch: int = 1) -> "OrderedDict[str, float]":
     for pfx, nseq in encs:
         o[pfx + "patch_embed"] = 2.0 * nseq * GG * D * 3 * P * P
         for i in range(cfg["depth"]):
-            o[f"{pfx}block{i}.qkv"] = 2.0 * nseq * T * 3 * D * D
-            o[f"{pfx}block{i}.attn"] = 4.0 * nseq * T * T * D
-            o[f"{pfx}block{i}.proj"] = 2.0 * nseq * T * D * D
-            o[f"{pfx}block{i}.fc1"] = 2.0 * nseq * T * M4 * D
-            o[f"{pfx}block{i}.fc2"] = 2.0 * nseq * T * D * M4
+            block_flops(o, f"{pfx}block{i}", nseq, T, D, cfg["mlp_hidden"])
     px = lambda k: float(k * k * GG)  # noqa: E731  pixels of a (k G)^2 map
     o["neck.image_block"] = 2.0 * px(1) * D * sd0 * 4
     o["neck.scaled0.proj"] = 2.0 * px(1) * D * sd0
@@ -104,8 +101,4 @@ def layer_class(name: str) -> str:
 
 
 def class_flops(cfg: dict, batch: int = 1) -> Dict[str, float]:
-    out: Dict[str, float] = {}
-    for k, v in layer_flops(cfg, batch).items():
-        c = layer_class(k)
-        out[c] = out.get(c, 0.0) + v
-    return out
+    return sum_classes(layer_flops(cfg, batch), layer_class)

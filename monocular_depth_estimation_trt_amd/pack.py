@@ -40,55 +40,49 @@ PACKER_VERSION = "mde-pack-1"
 ALIGN = 256
 
 
-def _pad2(a: np.ndarray, n_mult: int = 128, k_mult: int = 64) -> np.ndarray:
+def f32(a) -> np.ndarray:
+    """LayerNorm / LayerScale / bias vectors: flat fp32."""
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+
+
+def check_keys(sd: dict, keys, label: str = "") -> None:
+    """Raise if the state dict lacks a key the packer reads (`label`: the family, for the message)."""
+    missing = [k for k in keys if k not in sd and not k.endswith("mask_token")]
+    if missing:
+        raise KeyError(f"{label + ' ' if label else ''}state dict lacks {len(missing)} keys, e.g. {missing[:4]}")
+
+
+def _pad2(a: np.ndarray, dtype=np.float16) -> np.ndarray:
+    """[n][k] -> zero-padded [n -> x128][k -> x64 (f16) / x32 (fp32)]: the
+    weight operand of the MFMA GEMM (csrc/gemm.hip) / the exact-fp32 GEMM
+    (csrc/fp32.hip)."""
     n, k = a.shape
-    N = -(-n // n_mult) * n_mult
-    K = -(-k // k_mult) * k_mult
-    out = np.zeros((N, K), np.float16)
-    out[:n, :k] = a.astype(np.float16)
+    k_mult = 64 if dtype == np.float16 else 32
+    out = np.zeros((-(-n // 128) * 128, -(-k // k_mult) * k_mult), dtype)
+    out[:n, :k] = a
     return out
 
 
-def _pad2_f32(a: np.ndarray, n_mult: int = 128, k_mult: int = 32) -> np.ndarray:
-    """fp32 [Npad][Kpad] (N -> x128, K -> x32, zero padded): the exact-fp32
-    GEMM's weight operand (csrc/fp32.hip)."""
-    n, k = a.shape
-    out = np.zeros((-(-n // n_mult) * n_mult, -(-k // k_mult) * k_mult), np.float32)
-    out[:n, :k] = np.asarray(a, np.float32)
-    return out
+def _1x1(w: np.ndarray, dtype=np.float16) -> np.ndarray:
+    return _pad2(w.reshape(w.shape[0], -1), dtype)
 
 
-def _conv3(w: np.ndarray, cin_pad: int = 0) -> np.ndarray:
-    """[Cout][Cin][3][3] -> f16 [Cout_pad][9*Cin' pad64] in (ky, kx, ci) order,
+def _conv3(w: np.ndarray, dtype=np.float16, cin_pad: int = 0) -> np.ndarray:
+    """[Cout][Cin][3][3] -> [Cout_pad][9*Cin' padded] in (ky, kx, ci) order,
     Cin' = cin_pad (zero input channels appended) when given."""
     co, ci, kh, kw = w.shape
     assert kh == 3 and kw == 3, w.shape
     if cin_pad and cin_pad > ci:
         w = np.concatenate([w, np.zeros((co, cin_pad - ci, 3, 3), w.dtype)], axis=1)
         ci = cin_pad
-    return _pad2(np.ascontiguousarray(w.transpose(0, 2, 3, 1)).reshape(co, 9 * ci))
+    return _pad2(np.ascontiguousarray(w.transpose(0, 2, 3, 1)).reshape(co, 9 * ci), dtype)
 
 
-def _convT(w: np.ndarray) -> np.ndarray:
+def _convT(w: np.ndarray, dtype=np.float16) -> np.ndarray:
     """ConvTranspose2d weight [Cin][Cout][s][s] (k == s) -> [(dy*s+dx)*Cout+co][Cin]."""
     ci, co, s, s2 = w.shape
     assert s == s2
-    return _pad2(np.ascontiguousarray(w.transpose(2, 3, 1, 0)).reshape(s * s * co, ci))
-
-
-def _conv3_f32(w: np.ndarray) -> np.ndarray:
-    """[Cout][Cin][3][3] -> fp32 [Cout_pad][9*Cin pad32] in (ky, kx, ci) order:
-    the exact-fp32 implicit-im2col conv's weight operand (csrc/fp32.hip)."""
-    co, ci, kh, kw = w.shape
-    assert kh == 3 and kw == 3, w.shape
-    return _pad2_f32(np.ascontiguousarray(w.transpose(0, 2, 3, 1)).reshape(co, 9 * ci))
-
-
-def _convT_f32(w: np.ndarray) -> np.ndarray:
-    """ConvTranspose2d weight [Cin][Cout][s][s] (k == s) -> fp32 [(dy*s+dx)*Cout+co][Cin]."""
-    ci, co, s, s2 = w.shape
-    assert s == s2
-    return _pad2_f32(np.ascontiguousarray(w.transpose(2, 3, 1, 0)).reshape(s * s * co, ci))
+    return _pad2(np.ascontiguousarray(w.transpose(2, 3, 1, 0)).reshape(s * s * co, ci), dtype)
 
 
 def interpolate_pos_embed(pos: np.ndarray, ph: int, pw: int) -> np.ndarray:
@@ -146,32 +140,118 @@ def _slice_partials(v: np.ndarray) -> np.ndarray:
     return np.stack([h.sum(1), m2], 1).astype(np.float32).reshape(-1)
 
 
+def pack_block(o, sd, src: str, dst: str, hf: bool = False, qk_norm: bool = False, fold_ln: bool = False,
+               dtype=np.float16) -> None:
+    """One pre-LN ViT block's tensors, state-dict prefix `src` -> packed
+    prefix `dst`, in file order.  hf: transformers' DINOv2 key names with
+    split q / k / v (stored fused, rows [q; k; v]); qk_norm: VGGT's per-head
+    q/k LayerNorm; fold_ln: also the LayerNorm-folded qkv / fc1 (_fold_ln);
+    dtype float32: the exact-fp32 encoder's `.w32` linears."""
+    if hf:
+        qkv = [f"{src}attention.attention.{n}" for n in ("query", "key", "value")]
+        qkv_w = np.concatenate([sd[k + ".weight"] for k in qkv], 0)
+        qkv_b = np.concatenate([sd[k + ".bias"] for k in qkv], 0)
+        proj, ls1, ls2 = src + "attention.output.dense", "layer_scale1.lambda1", "layer_scale2.lambda1"
+    else:
+        qkv_w, qkv_b = sd[src + "attn.qkv.weight"], sd[src + "attn.qkv.bias"]
+        proj, ls1, ls2 = src + "attn.proj", "ls1.gamma", "ls2.gamma"
+    w = ".w32" if dtype == np.float32 else ".w"
+    o[dst + "ln1.g"] = f32(sd[src + "norm1.weight"])
+    o[dst + "ln1.b"] = f32(sd[src + "norm1.bias"])
+    o[dst + "qkv" + w] = _pad2(qkv_w, dtype)
+    o[dst + "qkv.b"] = f32(qkv_b)
+    if qk_norm:
+        o[dst + "qn.g"] = f32(sd[src + "attn.q_norm.weight"])
+        o[dst + "qn.b"] = f32(sd[src + "attn.q_norm.bias"])
+        o[dst + "kn.g"] = f32(sd[src + "attn.k_norm.weight"])
+        o[dst + "kn.b"] = f32(sd[src + "attn.k_norm.bias"])
+    o[dst + "proj" + w] = _pad2(sd[proj + ".weight"], dtype)
+    o[dst + "proj.b"] = f32(sd[proj + ".bias"])
+    o[dst + "ls1"] = f32(sd[src + ls1])
+    o[dst + "ln2.g"] = f32(sd[src + "norm2.weight"])
+    o[dst + "ln2.b"] = f32(sd[src + "norm2.bias"])
+    o[dst + "fc1" + w] = _pad2(sd[src + "mlp.fc1.weight"], dtype)
+    o[dst + "fc1.b"] = f32(sd[src + "mlp.fc1.bias"])
+    if fold_ln:
+        o[dst + "qkv.wf"], o[dst + "qkv.c1"], o[dst + "qkv.c2"] = _fold_ln(
+            qkv_w, qkv_b, sd[src + "norm1.weight"], sd[src + "norm1.bias"])
+        o[dst + "fc1.wf"], o[dst + "fc1.c1"], o[dst + "fc1.c2"] = _fold_ln(
+            sd[src + "mlp.fc1.weight"], sd[src + "mlp.fc1.bias"], sd[src + "norm2.weight"], sd[src + "norm2.bias"])
+    o[dst + "fc2" + w] = _pad2(sd[src + "mlp.fc2.weight"], dtype)
+    o[dst + "fc2.b"] = f32(sd[src + "mlp.fc2.bias"])
+    o[dst + "ls2"] = f32(sd[src + ls2])
+
+
+def pack_dpt_head(o, sd, cfg: dict, dtype=np.float16, fold_norm=None, pe=None, rf4_unit1: bool = True,
+                  depth_only: bool = False) -> None:
+    """The upstream DPT head ("depth_head.") in file order.  dtype float32:
+    the exact-fp32 engine's `.w32` weights, no channel padding (the fp32 conv
+    takes any channel count % 4).  fold_norm = (gamma, beta): the taps' final
+    LayerNorm folded into the projects (`projN.wf/.c1/.c2`, engine.hip).
+    VGGT: pe = (4 per-projection tables `peN`, `head.pe`), no resConfUnit1 in
+    refinenet4, output_conv2's last 1x1 reduced to its depth channel."""
+    h = "depth_head."
+    w = ".w32" if dtype == np.float32 else ".w"
+    for i in range(4):
+        pw = sd[f"{h}projects.{i}.weight"]
+        pw = pw.reshape(pw.shape[0], pw.shape[1])
+        o[f"proj{i}{w}"] = _pad2(pw, dtype)
+        o[f"proj{i}.b"] = f32(sd[f"{h}projects.{i}.bias"])
+        if fold_norm is not None:
+            o[f"proj{i}.wf"], o[f"proj{i}.c1"], o[f"proj{i}.c2"] = _fold_ln(pw, sd[f"{h}projects.{i}.bias"], *fold_norm)
+        if pe is not None:
+            o[f"pe{i}"] = pe[0][i]
+    o["rs0" + w] = _convT(sd[h + "resize_layers.0.weight"], dtype)
+    o["rs0.b"] = f32(sd[h + "resize_layers.0.bias"])
+    o["rs1" + w] = _convT(sd[h + "resize_layers.1.weight"], dtype)
+    o["rs1.b"] = f32(sd[h + "resize_layers.1.bias"])
+    o["rs3" + w] = _conv3(sd[h + "resize_layers.3.weight"], dtype)
+    o["rs3.b"] = f32(sd[h + "resize_layers.3.bias"])
+    for i in range(4):
+        # f16 DPT maps feeding the direct conv carry channels padded to x32 (48 -> 64)
+        cin_pad = -(-cfg["out_channels"][i] // 32) * 32 if dtype == np.float16 else 0
+        o[f"rn{i + 1}{w}"] = _conv3(sd[f"{h}scratch.layer{i + 1}_rn.weight"], dtype, cin_pad)
+    for r in range(1, 5):
+        s = f"{h}scratch.refinenet{r}."
+        o[f"rf{r}.out{w}"] = _1x1(sd[s + "out_conv.weight"], dtype)
+        o[f"rf{r}.out.b"] = f32(sd[s + "out_conv.bias"])
+        for u in ((1, 2) if r < 4 or rf4_unit1 else (2,)):
+            for c in (1, 2):
+                o[f"rf{r}.rcu{u}.c{c}{w}"] = _conv3(sd[f"{s}resConfUnit{u}.conv{c}.weight"], dtype)
+                o[f"rf{r}.rcu{u}.c{c}.b"] = f32(sd[f"{s}resConfUnit{u}.conv{c}.bias"])
+    s = h + "scratch."
+    o["head.c1" + w] = _conv3(sd[s + "output_conv1.weight"], dtype)
+    o["head.c1.b"] = f32(sd[s + "output_conv1.bias"])
+    o["head.c2" + w] = _conv3(sd[s + "output_conv2.0.weight"], dtype)
+    o["head.c2.b"] = f32(sd[s + "output_conv2.0.bias"])
+    if pe is not None:
+        o["head.pe"] = pe[1]
+    rows = slice(0, 1) if depth_only else slice(None)
+    o["head.c3.w"] = f32(sd[s + "output_conv2.2.weight"][rows])
+    o["head.c3.b"] = f32(sd[s + "output_conv2.2.bias"][rows])
+
+
 def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict, img_h: int, img_w: int,
                    fold_ln: bool = False, enc_f32: bool = False) -> "OrderedDict[str, np.ndarray]":
     """The packed tensors (name -> f16/f32 numpy array) for one input size.
     fold_ln (precision "fp16" engines) adds the LayerNorm-folded qkv / fc1 /
     DPT project weights (`*.wf`, `*.c1`, `*.c2`) and the cls row's partials
-    (`pos.cls.st`).  enc_f32 (precision "fp32" engines) stores the patch
-    embed and the block linears as fp32 (`*.w32`) in place of f16."""
+    (`pos.cls.st`).  enc_f32 (precision "fp32" engines) stores every conv /
+    linear weight as fp32 (`*.w32`) in place of f16: the exact-fp32 encoder
+    and the head run on fp32 maps (engine.hip dav2_head32)."""
     sd = normalize_keys(sd)
-    missing = [k for k in W.expected_keys(cfg) if k not in sd and not k.endswith("mask_token")]
-    if missing:
-        raise KeyError(f"state dict lacks {len(missing)} keys, e.g. {missing[:4]}")
+    check_keys(sd, W.expected_keys(cfg))
     P = cfg["patch"]
     if img_h % P or img_w % P:
         raise ValueError(f"input size {img_h}x{img_w} is not a multiple of the patch size {P}")
     ph, pw = img_h // P, img_w // P
     D = cfg["embed_dim"]
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)  # noqa: E731
+    dtype = np.float32 if enc_f32 else np.float16
     o: "OrderedDict[str, np.ndarray]" = OrderedDict()
     p = "pretrained."
-    pe = sd[p + "patch_embed.proj.weight"]                   # [D,3,14,14]
     pe16 = np.zeros((D, 3, 14, 16), np.float32)
-    pe16[..., :14] = pe
-    if enc_f32:
-        o["patch.w32"] = _pad2_f32(pe16.reshape(D, 3 * 14 * 16))
-    else:
-        o["patch.w"] = _pad2(pe16.reshape(D, 3 * 14 * 16))
+    pe16[..., :14] = sd[p + "patch_embed.proj.weight"]      # [D,3,14,14]
+    o["patch.w32" if enc_f32 else "patch.w"] = _pad2(pe16.reshape(D, 3 * 14 * 16), dtype)
     o["patch.b"] = f32(sd[p + "patch_embed.proj.bias"])
     pos = interpolate_pos_embed(sd[p + "pos_embed"], ph, pw)
     o["pos.patch"] = np.ascontiguousarray(pos[0, 1:], dtype=np.float32)
@@ -179,105 +259,12 @@ def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict, img_h: int, img_w: int,
     if fold_ln and D % 32 == 0:
         o["pos.cls.st"] = _slice_partials(o["pos.cls"])
     for i in range(cfg["depth"]):
-        b = f"{p}blocks.{i}."
-        q = f"b{i}."
-        o[q + "ln1.g"] = f32(sd[b + "norm1.weight"])
-        o[q + "ln1.b"] = f32(sd[b + "norm1.bias"])
-        lin = (lambda a: _pad2_f32(a)) if enc_f32 else _pad2  # noqa: E731
-        wsuf = ".w32" if enc_f32 else ".w"
-        o[q + "qkv" + wsuf] = lin(sd[b + "attn.qkv.weight"])
-        o[q + "qkv.b"] = f32(sd[b + "attn.qkv.bias"])
-        o[q + "proj" + wsuf] = lin(sd[b + "attn.proj.weight"])
-        o[q + "proj.b"] = f32(sd[b + "attn.proj.bias"])
-        o[q + "ls1"] = f32(sd[b + "ls1.gamma"])
-        o[q + "ln2.g"] = f32(sd[b + "norm2.weight"])
-        o[q + "ln2.b"] = f32(sd[b + "norm2.bias"])
-        o[q + "fc1" + wsuf] = lin(sd[b + "mlp.fc1.weight"])
-        o[q + "fc1.b"] = f32(sd[b + "mlp.fc1.bias"])
-        if fold_ln:
-            o[q + "qkv.wf"], o[q + "qkv.c1"], o[q + "qkv.c2"] = _fold_ln(
-                sd[b + "attn.qkv.weight"], sd[b + "attn.qkv.bias"], sd[b + "norm1.weight"], sd[b + "norm1.bias"])
-            o[q + "fc1.wf"], o[q + "fc1.c1"], o[q + "fc1.c2"] = _fold_ln(
-                sd[b + "mlp.fc1.weight"], sd[b + "mlp.fc1.bias"], sd[b + "norm2.weight"], sd[b + "norm2.bias"])
-        o[q + "fc2" + wsuf] = lin(sd[b + "mlp.fc2.weight"])
-        o[q + "fc2.b"] = f32(sd[b + "mlp.fc2.bias"])
-        o[q + "ls2"] = f32(sd[b + "ls2.gamma"])
+        pack_block(o, sd, f"{p}blocks.{i}.", f"b{i}.", fold_ln=fold_ln, dtype=dtype)
     o["norm.g"] = f32(sd[p + "norm.weight"])
     o["norm.b"] = f32(sd[p + "norm.bias"])
-    h = "depth_head."
-    if enc_f32:
-        # the exact-fp32 engine's DPT head: every conv / linear weight fp32
-        # (`*.w32`), the head run on fp32 maps (engine.hip dav2_head32)
-        _head_f32(sd, cfg, o, f32)
-        return o
-    for i in range(4):
-        w = sd[f"{h}projects.{i}.weight"]
-        o[f"proj{i}.w"] = _pad2(w.reshape(w.shape[0], w.shape[1]))
-        o[f"proj{i}.b"] = f32(sd[f"{h}projects.{i}.bias"])
-        if fold_ln:  # the taps' final LayerNorm folded into the projects (engine.hip)
-            o[f"proj{i}.wf"], o[f"proj{i}.c1"], o[f"proj{i}.c2"] = _fold_ln(
-                w.reshape(w.shape[0], w.shape[1]), sd[f"{h}projects.{i}.bias"], sd[p + "norm.weight"],
-                sd[p + "norm.bias"])
-    o["rs0.w"] = _convT(sd[h + "resize_layers.0.weight"])
-    o["rs0.b"] = f32(sd[h + "resize_layers.0.bias"])
-    o["rs1.w"] = _convT(sd[h + "resize_layers.1.weight"])
-    o["rs1.b"] = f32(sd[h + "resize_layers.1.bias"])
-    o["rs3.w"] = _conv3(sd[h + "resize_layers.3.weight"])
-    o["rs3.b"] = f32(sd[h + "resize_layers.3.bias"])
-    for i in range(4):
-        # DPT maps feeding the direct conv carry channels padded to x32 (48 -> 64)
-        o[f"rn{i + 1}.w"] = _conv3(sd[f"{h}scratch.layer{i + 1}_rn.weight"], -(-cfg["out_channels"][i] // 32) * 32)
-    for r in range(1, 5):
-        s = f"{h}scratch.refinenet{r}."
-        w = sd[s + "out_conv.weight"]
-        o[f"rf{r}.out.w"] = _pad2(w.reshape(w.shape[0], w.shape[1]))
-        o[f"rf{r}.out.b"] = f32(sd[s + "out_conv.bias"])
-        for u in (1, 2):
-            for c in (1, 2):
-                o[f"rf{r}.rcu{u}.c{c}.w"] = _conv3(sd[f"{s}resConfUnit{u}.conv{c}.weight"])
-                o[f"rf{r}.rcu{u}.c{c}.b"] = f32(sd[f"{s}resConfUnit{u}.conv{c}.bias"])
-    s = h + "scratch."
-    o["head.c1.w"] = _conv3(sd[s + "output_conv1.weight"])
-    o["head.c1.b"] = f32(sd[s + "output_conv1.bias"])
-    o["head.c2.w"] = _conv3(sd[s + "output_conv2.0.weight"])
-    o["head.c2.b"] = f32(sd[s + "output_conv2.0.bias"])
-    o["head.c3.w"] = f32(sd[s + "output_conv2.2.weight"])
-    o["head.c3.b"] = f32(sd[s + "output_conv2.2.bias"])
+    fold = fold_ln and not enc_f32
+    pack_dpt_head(o, sd, cfg, dtype, fold_norm=(sd[p + "norm.weight"], sd[p + "norm.bias"]) if fold else None)
     return o
-
-
-def _head_f32(sd, cfg, o, f32) -> None:
-    """fp32 DPT head weights: the f16 head's tensors under `.w32` names, no
-    channel padding (the fp32 conv takes any channel count % 4)."""
-    h = "depth_head."
-    for i in range(4):
-        w = sd[f"{h}projects.{i}.weight"]
-        o[f"proj{i}.w32"] = _pad2_f32(w.reshape(w.shape[0], w.shape[1]))
-        o[f"proj{i}.b"] = f32(sd[f"{h}projects.{i}.bias"])
-    o["rs0.w32"] = _convT_f32(sd[h + "resize_layers.0.weight"])
-    o["rs0.b"] = f32(sd[h + "resize_layers.0.bias"])
-    o["rs1.w32"] = _convT_f32(sd[h + "resize_layers.1.weight"])
-    o["rs1.b"] = f32(sd[h + "resize_layers.1.bias"])
-    o["rs3.w32"] = _conv3_f32(sd[h + "resize_layers.3.weight"])
-    o["rs3.b"] = f32(sd[h + "resize_layers.3.bias"])
-    for i in range(4):
-        o[f"rn{i + 1}.w32"] = _conv3_f32(sd[f"{h}scratch.layer{i + 1}_rn.weight"])
-    for r in range(1, 5):
-        s = f"{h}scratch.refinenet{r}."
-        w = sd[s + "out_conv.weight"]
-        o[f"rf{r}.out.w32"] = _pad2_f32(w.reshape(w.shape[0], w.shape[1]))
-        o[f"rf{r}.out.b"] = f32(sd[s + "out_conv.bias"])
-        for u in (1, 2):
-            for c in (1, 2):
-                o[f"rf{r}.rcu{u}.c{c}.w32"] = _conv3_f32(sd[f"{s}resConfUnit{u}.conv{c}.weight"])
-                o[f"rf{r}.rcu{u}.c{c}.b"] = f32(sd[f"{s}resConfUnit{u}.conv{c}.bias"])
-    s = h + "scratch."
-    o["head.c1.w32"] = _conv3_f32(sd[s + "output_conv1.weight"])
-    o["head.c1.b"] = f32(sd[s + "output_conv1.bias"])
-    o["head.c2.w32"] = _conv3_f32(sd[s + "output_conv2.0.weight"])
-    o["head.c2.b"] = f32(sd[s + "output_conv2.0.bias"])
-    o["head.c3.w"] = f32(sd[s + "output_conv2.2.weight"])
-    o["head.c3.b"] = f32(sd[s + "output_conv2.2.bias"])
 
 
 INPUT_FORMATS = ("float32_nchw", "uint8_nhwc")
@@ -286,6 +273,38 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
 PRECISIONS = ("fp16", "fp32")
+
+# PackConfig (csrc/pack_format.h) in struct order: (field, struct format); `reserved` pads it to 256 bytes
+_CONFIG_FIELDS = (
+    ("embed_dim", "i"), ("depth", "i"), ("num_heads", "i"), ("mlp_hidden", "i"), ("patch", "i"),
+    ("img_h", "i"), ("img_w", "i"), ("features", "i"), ("out_channels", "4i"), ("taps", "4i"),
+    ("head_hidden", "i"), ("metric", "i"), ("max_depth", "f"), ("ln_eps", "f"), ("encoder", "16s"),
+    ("input_u8", "i"), ("in_scale", "f"), ("in_mean", "3f"), ("in_std", "3f"),
+    ("family", "i"), ("vit_size", "i"), ("merge_pad", "i"), ("use_fov", "i"), ("fov_layers", "i"), ("fov_k", "i"),
+    ("hooks", "2i"), ("inter_dims", "2i"), ("scaled_dims", "3i"),
+    ("frames", "i"), ("npre", "i"), ("aa_depth", "i"), ("agg_eps", "f"), ("resid_f16", "i"), ("enc_f32", "i"))
+_CONFIG_STRUCT = struct.Struct("<" + "".join(fmt for _, fmt in _CONFIG_FIELDS))
+assert _CONFIG_STRUCT.size == 256 - 52, _CONFIG_STRUCT.size     # sizeof(PackConfig) - sizeof(reserved)
+
+
+def pack_config(cfg: dict, **fields) -> bytes:
+    """The 256 PackConfig bytes: the ViT geometry every family stores
+    (embed_dim, depth, num_heads, mlp_hidden, patch, head_hidden, ln_eps,
+    encoder) from cfg, the other fields by name; what is not named is zero."""
+    fields.update({k: cfg[k] for k in ("embed_dim", "depth", "num_heads", "mlp_hidden", "patch", "head_hidden",
+                                       "ln_eps")}, encoder=cfg["encoder"].encode()[:15])
+    vals = []
+    for name, fmt in _CONFIG_FIELDS:
+        v = fields.pop(name, None)
+        if len(fmt) == 1 or fmt[-1] == "s":
+            vals.append(v if v is not None else (b"" if fmt[-1] == "s" else 0))
+        else:
+            v = list(v) if v is not None else [0] * int(fmt[:-1])
+            assert len(v) == int(fmt[:-1]), (name, v)
+            vals += v
+    if fields:
+        raise TypeError(f"no PackConfig field named {sorted(fields)}")
+    return _CONFIG_STRUCT.pack(*vals) + b"\0" * 52
 
 
 def _config_bytes(cfg: dict, img_h: int, img_w: int, input_format: str = "float32_nchw",
@@ -301,22 +320,15 @@ def _config_bytes(cfg: dict, img_h: int, img_w: int, input_format: str = "float3
         raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
     if input_format not in INPUT_FORMATS:
         raise ValueError(f"input_format must be one of {INPUT_FORMATS}, got {input_format!r}")
-    oc, taps = cfg["out_channels"], cfg["taps"]
-    b = struct.pack("<8i4i4i2i2f16s", cfg["embed_dim"], cfg["depth"], cfg["num_heads"], cfg["mlp_hidden"],
-                    cfg["patch"], img_h, img_w, cfg["features"], *oc, *taps, cfg["head_hidden"],
-                    1 if cfg["depth_type"] == "metric" else 0, float(cfg["max_depth"]), float(cfg["ln_eps"]),
-                    cfg["encoder"].encode()[:15])
-    assert len(b) == 96, len(b)
     u8 = input_format == "uint8_nhwc"
     if u8 and (len(mean) != 3 or len(std) != 3 or float(scale) == 0.0 or any(float(v) == 0.0 for v in std)):
         raise ValueError("uint8 preamble needs 3 means, 3 non-zero stds and a non-zero scale")
-    b += struct.pack("<if3f3f", 1 if u8 else 0, float(scale) if u8 else 0.0,
-                     *([float(v) for v in mean] if u8 else [0.0] * 3),
-                     *([float(v) for v in std] if u8 else [0.0] * 3))
-    assert len(b) == 128, len(b)
-    b += b"\0" * 68 + struct.pack("<i", 1 if precision == "fp16" else 0)   # resid_f16 at byte 196
-    b += struct.pack("<i", 1 if precision == "fp32" else 0)                 # enc_f32 at byte 200
-    return b + b"\0" * 52
+    pre = dict(input_u8=1, in_scale=float(scale), in_mean=[float(v) for v in mean],
+               in_std=[float(v) for v in std]) if u8 else {}
+    return pack_config(cfg, img_h=img_h, img_w=img_w, features=cfg["features"], out_channels=cfg["out_channels"],
+                       taps=cfg["taps"], metric=1 if cfg["depth_type"] == "metric" else 0,
+                       max_depth=float(cfg["max_depth"]), resid_f16=1 if precision == "fp16" else 0,
+                       enc_f32=1 if precision == "fp32" else 0, **pre)
 
 
 def container(tens: "OrderedDict[str, np.ndarray]", cfg_bytes: bytes) -> bytes:

@@ -22,7 +22,6 @@ checkpoint layout, weights_depth_pro.py).
 
 from __future__ import annotations
 
-import struct
 from collections import OrderedDict
 from typing import Dict
 
@@ -30,13 +29,13 @@ import numpy as np
 
 from . import pack as PK
 from . import weights_depth_pro as WD
+from .pack import f32
 
 FAMILY_DEPTH_PRO = 1
 
 
 def _vit(o, sd, src: str, dst: str, cfg: dict):
     D, P = cfg["embed_dim"], cfg["patch"]
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)  # noqa: E731
     e = src + "embeddings."
     o[dst + "patch.w"] = PK._pad2(sd[e + "patch_embeddings.projection.weight"].reshape(D, 3 * P * P))
     o[dst + "patch.b"] = f32(sd[e + "patch_embeddings.projection.bias"])
@@ -44,29 +43,9 @@ def _vit(o, sd, src: str, dst: str, cfg: dict):
     o[dst + "pos.patch"] = np.ascontiguousarray(pos[0, 1:], dtype=np.float32)
     o[dst + "pos.cls"] = f32(sd[e + "cls_token"].reshape(-1) + pos[0, 0])
     for i in range(cfg["depth"]):
-        b = f"{src}encoder.layer.{i}."
-        a = b + "attention.attention."
-        q = f"{dst}b{i}."
-        o[q + "ln1.g"] = f32(sd[b + "norm1.weight"])
-        o[q + "ln1.b"] = f32(sd[b + "norm1.bias"])
-        o[q + "qkv.w"] = PK._pad2(np.concatenate([sd[a + n + ".weight"] for n in ("query", "key", "value")], 0))
-        o[q + "qkv.b"] = f32(np.concatenate([sd[a + n + ".bias"] for n in ("query", "key", "value")], 0))
-        o[q + "proj.w"] = PK._pad2(sd[b + "attention.output.dense.weight"])
-        o[q + "proj.b"] = f32(sd[b + "attention.output.dense.bias"])
-        o[q + "ls1"] = f32(sd[b + "layer_scale1.lambda1"])
-        o[q + "ln2.g"] = f32(sd[b + "norm2.weight"])
-        o[q + "ln2.b"] = f32(sd[b + "norm2.bias"])
-        o[q + "fc1.w"] = PK._pad2(sd[b + "mlp.fc1.weight"])
-        o[q + "fc1.b"] = f32(sd[b + "mlp.fc1.bias"])
-        o[q + "fc2.w"] = PK._pad2(sd[b + "mlp.fc2.weight"])
-        o[q + "fc2.b"] = f32(sd[b + "mlp.fc2.bias"])
-        o[q + "ls2"] = f32(sd[b + "layer_scale2.lambda1"])
+        PK.pack_block(o, sd, f"{src}encoder.layer.{i}.", f"{dst}b{i}.", hf=True)
     o[dst + "norm.g"] = f32(sd[src + "layernorm.weight"])
     o[dst + "norm.b"] = f32(sd[src + "layernorm.bias"])
-
-
-def _1x1(w: np.ndarray) -> np.ndarray:
-    return PK._pad2(w.reshape(w.shape[0], -1))
 
 
 def fold_deconv_projection(wt: np.ndarray, wp: np.ndarray) -> np.ndarray:
@@ -78,10 +57,7 @@ def fold_deconv_projection(wt: np.ndarray, wp: np.ndarray) -> np.ndarray:
 
 def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict) -> "OrderedDict[str, np.ndarray]":
     sd = PK.normalize_keys(sd)
-    missing = [k for k in WD.expected_keys(cfg) if k not in sd and not k.endswith("mask_token")]
-    if missing:
-        raise KeyError(f"Depth Pro state dict lacks {len(missing)} keys, e.g. {missing[:4]}")
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)  # noqa: E731
+    PK.check_keys(sd, WD.expected_keys(cfg), "Depth Pro")
     o: "OrderedDict[str, np.ndarray]" = OrderedDict()
     _vit(o, sd, "depth_pro.encoder.patch_encoder.model.", "pe.", cfg)
     _vit(o, sd, "depth_pro.encoder.image_encoder.model.", "ie.", cfg)
@@ -91,14 +67,14 @@ def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict) -> "OrderedDict[str, np
     o["img.up.w"] = PK._convT(sd[u + "image_block.layers.0.weight"])
     o["img.up.b"] = f32(sd[u + "image_block.layers.0.bias"])
     for i in range(len(cfg["scaled_dims"])):
-        o[f"s{i}.proj.w"] = _1x1(sd[f"{u}scaled_images.{i}.layers.0.weight"])
+        o[f"s{i}.proj.w"] = PK._1x1(sd[f"{u}scaled_images.{i}.layers.0.weight"])
         o[f"s{i}.up.w"] = PK._convT(sd[f"{u}scaled_images.{i}.layers.1.weight"])
     for i in range(len(cfg["inter_dims"])):
-        o[f"h{i}.proj.w"] = _1x1(sd[f"{u}intermediate.{i}.layers.0.weight"])
+        o[f"h{i}.proj.w"] = PK._1x1(sd[f"{u}intermediate.{i}.layers.0.weight"])
         for j in range(2 + i):
             o[f"h{i}.up{j}.w"] = PK._convT(sd[f"{u}intermediate.{i}.layers.{j + 1}.weight"])
     n = "depth_pro.neck."
-    o["fuse.w"] = _1x1(sd[n + "fuse_image_with_low_res.weight"])
+    o["fuse.w"] = PK._1x1(sd[n + "fuse_image_with_low_res.weight"])
     o["fuse.b"] = f32(sd[n + "fuse_image_with_low_res.bias"])
     for i in range(5):
         k = f"{n}feature_projection.projections.{i}.weight"
@@ -118,7 +94,7 @@ def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict) -> "OrderedDict[str, np
             o[dst + "up.w"] = PK._convT(fold_deconv_projection(sd[src + "deconv.weight"], sd[src + "projection.weight"]))
             o[dst + "up.b"] = f32(sd[src + "projection.bias"])
         else:
-            o[dst + "out.w"] = _1x1(sd[src + "projection.weight"])
+            o[dst + "out.w"] = PK._1x1(sd[src + "projection.weight"])
             o[dst + "out.b"] = f32(sd[src + "projection.bias"])
     o["head.c1.w"] = PK._conv3(sd["head.layers.0.weight"])
     o["head.c1.b"] = f32(sd["head.layers.0.bias"])
@@ -145,20 +121,14 @@ def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict) -> "OrderedDict[str, np
 
 def config_bytes(cfg: dict) -> bytes:
     """PackConfig (csrc/pack_format.h) with family = 1 and the Depth Pro geometry."""
-    S = cfg["img"]
-    b = struct.pack("<8i4i4i2i2f16s", cfg["embed_dim"], cfg["depth"], cfg["num_heads"], cfg["mlp_hidden"],
-                    cfg["patch"], S, S, cfg["fusion"], 0, 0, 0, 0, 0, 0, 0, 0, cfg["head_hidden"], 0, 0.0,
-                    float(cfg["ln_eps"]), cfg["encoder"].encode()[:15])
-    b += struct.pack("<if3f3f", 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
-    assert len(b) == 128, len(b)
     hooks, idims, sdims = cfg["hooks"], cfg["inter_dims"], cfg["scaled_dims"]
     if len(hooks) != 2 or len(idims) != 2 or len(sdims) != 3 or list(cfg["ratios"]) != [0.25, 0.5, 1.0] \
             or list(cfg["overlaps"]) != [0.0, 0.5, 0.25]:
         raise ValueError("the packed engine supports the upstream Depth Pro pyramid / hook layout only")
-    b += struct.pack("<6i2i2i3i", FAMILY_DEPTH_PRO, cfg["vit_size"], cfg["merge_pad"], 1 if cfg["use_fov"] else 0,
-                     cfg["fov_layers"], WD.fov_final_kernel(cfg), *hooks, *idims, *sdims)
-    assert len(b) == 180, len(b)
-    return b + b"\0" * 76
+    return PK.pack_config(cfg, img_h=cfg["img"], img_w=cfg["img"], features=cfg["fusion"], family=FAMILY_DEPTH_PRO,
+                          vit_size=cfg["vit_size"], merge_pad=cfg["merge_pad"], use_fov=1 if cfg["use_fov"] else 0,
+                          fov_layers=cfg["fov_layers"], fov_k=WD.fov_final_kernel(cfg), hooks=hooks,
+                          inter_dims=idims, scaled_dims=sdims)
 
 
 def pack_bytes(sd: Dict[str, np.ndarray], cfg: dict) -> bytes:

@@ -31,7 +31,6 @@ its static [1, S, 3, 518, 518] profile.
 
 from __future__ import annotations
 
-import struct
 from collections import OrderedDict
 from typing import Dict, Tuple
 
@@ -39,6 +38,7 @@ import numpy as np
 
 from . import pack as PK
 from . import weights_vggt as WV
+from .pack import f32
 
 FAMILY_VGGT = 2
 NPRE = 1 + WV.NUM_REG      # camera + 4 register tokens ahead of the patch tokens
@@ -104,39 +104,13 @@ def head_pe(w_conv: np.ndarray, h: int, w: int, ratio: float = 0.1, omega_0: flo
 
 
 # ---- packing ----------------------------------------------------------------
-def _blk(o, sd, src: str, dst: str, qk_norm: bool):
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)  # noqa: E731
-    o[dst + "ln1.g"] = f32(sd[src + "norm1.weight"])
-    o[dst + "ln1.b"] = f32(sd[src + "norm1.bias"])
-    o[dst + "qkv.w"] = PK._pad2(sd[src + "attn.qkv.weight"])
-    o[dst + "qkv.b"] = f32(sd[src + "attn.qkv.bias"])
-    if qk_norm:
-        o[dst + "qn.g"] = f32(sd[src + "attn.q_norm.weight"])
-        o[dst + "qn.b"] = f32(sd[src + "attn.q_norm.bias"])
-        o[dst + "kn.g"] = f32(sd[src + "attn.k_norm.weight"])
-        o[dst + "kn.b"] = f32(sd[src + "attn.k_norm.bias"])
-    o[dst + "proj.w"] = PK._pad2(sd[src + "attn.proj.weight"])
-    o[dst + "proj.b"] = f32(sd[src + "attn.proj.bias"])
-    o[dst + "ls1"] = f32(sd[src + "ls1.gamma"])
-    o[dst + "ln2.g"] = f32(sd[src + "norm2.weight"])
-    o[dst + "ln2.b"] = f32(sd[src + "norm2.bias"])
-    o[dst + "fc1.w"] = PK._pad2(sd[src + "mlp.fc1.weight"])
-    o[dst + "fc1.b"] = f32(sd[src + "mlp.fc1.bias"])
-    o[dst + "fc2.w"] = PK._pad2(sd[src + "mlp.fc2.weight"])
-    o[dst + "fc2.b"] = f32(sd[src + "mlp.fc2.bias"])
-    o[dst + "ls2"] = f32(sd[src + "ls2.gamma"])
-
-
 def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict) -> "OrderedDict[str, np.ndarray]":
     sd = PK.normalize_keys(sd)
-    missing = [k for k in WV.expected_keys(cfg) if k not in sd and not k.endswith("mask_token")]
-    if missing:
-        raise KeyError(f"VGGT state dict lacks {len(missing)} keys, e.g. {missing[:4]}")
+    PK.check_keys(sd, WV.expected_keys(cfg), "VGGT")
     D, P, S = cfg["embed_dim"], cfg["patch"], cfg["img"]
     g = S // P
     np_ = g * g
     oc = cfg["out_channels"]
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32).reshape(-1)  # noqa: E731
     o: "OrderedDict[str, np.ndarray]" = OrderedDict()
     p = "aggregator.patch_embed."
     pw, pb = fold_patch_embed(sd[p + "patch_embed.proj.weight"], sd[p + "patch_embed.proj.bias"])
@@ -153,7 +127,7 @@ def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict) -> "OrderedDict[str, np
         [sd[p + "cls_token"].reshape(1, D) + pos[0, :1], sd[p + "register_tokens"].reshape(WV.NUM_REG, D)], 0),
         dtype=np.float32)
     for i in range(cfg["depth"]):
-        _blk(o, sd, f"{p}blocks.{i}.", f"db{i}.", False)
+        PK.pack_block(o, sd, f"{p}blocks.{i}.", f"db{i}.")
     o["norm.g"] = f32(sd[p + "norm.weight"])
     o["norm.b"] = f32(sd[p + "norm.bias"])
     a = "aggregator."
@@ -161,45 +135,17 @@ def packed_tensors(sd: Dict[str, np.ndarray], cfg: dict) -> "OrderedDict[str, np
     reg = sd[a + "register_token"].reshape(2, WV.NUM_REG, D)
     o["pre.agg"] = np.ascontiguousarray(np.concatenate([cam, reg], 1), dtype=np.float32)   # [2][5][D]
     for i in range(cfg["aa_depth"]):
-        _blk(o, sd, f"{a}frame_blocks.{i}.", f"fb{i}.", True)
-        _blk(o, sd, f"{a}global_blocks.{i}.", f"gb{i}.", True)
+        PK.pack_block(o, sd, f"{a}frame_blocks.{i}.", f"fb{i}.", qk_norm=True)
+        PK.pack_block(o, sd, f"{a}global_blocks.{i}.", f"gb{i}.", qk_norm=True)
     cos, sin = rope_tables(g + 2, 32, cfg["rope_freq"])
     o["rope.cos"] = cos
     o["rope.sin"] = sin
     h = "depth_head."
     o["dh.norm.g"] = f32(sd[h + "norm.weight"])
     o["dh.norm.b"] = f32(sd[h + "norm.bias"])
-    for i in range(4):
-        w = sd[f"{h}projects.{i}.weight"]
-        o[f"proj{i}.w"] = PK._pad2(w.reshape(w.shape[0], w.shape[1]))
-        o[f"proj{i}.b"] = f32(sd[f"{h}projects.{i}.bias"])
-        o[f"pe{i}"] = uv_embed(oc[i], g, g, 1.0, cfg["pe_ratio"], cfg["pe_omega"]).astype(np.float16)
-    o["rs0.w"] = PK._convT(sd[h + "resize_layers.0.weight"])
-    o["rs0.b"] = f32(sd[h + "resize_layers.0.bias"])
-    o["rs1.w"] = PK._convT(sd[h + "resize_layers.1.weight"])
-    o["rs1.b"] = f32(sd[h + "resize_layers.1.bias"])
-    o["rs3.w"] = PK._conv3(sd[h + "resize_layers.3.weight"])
-    o["rs3.b"] = f32(sd[h + "resize_layers.3.bias"])
-    for i in range(4):
-        o[f"rn{i + 1}.w"] = PK._conv3(sd[f"{h}scratch.layer{i + 1}_rn.weight"], -(-oc[i] // 32) * 32)
-    for r in range(1, 5):
-        s = f"{h}scratch.refinenet{r}."
-        w = sd[s + "out_conv.weight"]
-        o[f"rf{r}.out.w"] = PK._pad2(w.reshape(w.shape[0], w.shape[1]))
-        o[f"rf{r}.out.b"] = f32(sd[s + "out_conv.bias"])
-        for u in ((2,) if r == 4 else (1, 2)):
-            for c in (1, 2):
-                o[f"rf{r}.rcu{u}.c{c}.w"] = PK._conv3(sd[f"{s}resConfUnit{u}.conv{c}.weight"])
-                o[f"rf{r}.rcu{u}.c{c}.b"] = f32(sd[f"{s}resConfUnit{u}.conv{c}.bias"])
-    s = h + "scratch."
-    o["head.c1.w"] = PK._conv3(sd[s + "output_conv1.weight"])
-    o["head.c1.b"] = f32(sd[s + "output_conv1.bias"])
-    w2 = sd[s + "output_conv2.0.weight"]
-    o["head.c2.w"] = PK._conv3(w2)
-    o["head.c2.b"] = f32(sd[s + "output_conv2.0.bias"])
-    o["head.pe"] = head_pe(w2, S, S, cfg["pe_ratio"], cfg["pe_omega"]).astype(np.float16)
-    o["head.c3.w"] = f32(sd[s + "output_conv2.2.weight"][0])          # depth channel only
-    o["head.c3.b"] = f32(sd[s + "output_conv2.2.bias"][:1])
+    pe = [uv_embed(oc[i], g, g, 1.0, cfg["pe_ratio"], cfg["pe_omega"]).astype(np.float16) for i in range(4)]
+    pe_head = head_pe(sd[h + "scratch.output_conv2.0.weight"], S, S, cfg["pe_ratio"], cfg["pe_omega"])
+    PK.pack_dpt_head(o, sd, cfg, pe=(pe, pe_head.astype(np.float16)), rf4_unit1=False, depth_only=True)
     return o
 
 
@@ -210,17 +156,9 @@ def config_bytes(cfg: dict, frames: int) -> bytes:
     (frames, special tokens, aggregator depth, aggregator LayerNorm eps)."""
     if frames < 1:
         raise ValueError(f"frames must be >= 1, got {frames}")
-    S = cfg["img"]
-    b = struct.pack("<8i4i4i2i2f16s", cfg["embed_dim"], cfg["depth"], cfg["num_heads"], cfg["mlp_hidden"],
-                    cfg["patch"], S, S, cfg["features"], *cfg["out_channels"], *cfg["taps"], cfg["head_hidden"], 2,
-                    0.0, float(cfg["ln_eps"]), cfg["encoder"].encode()[:15])
-    b += struct.pack("<if3f3f", 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
-    assert len(b) == 128, len(b)
-    b += struct.pack("<6i2i2i3i", FAMILY_VGGT, *([0] * 12))
-    assert len(b) == 180, len(b)
-    b += struct.pack("<3if", int(frames), NPRE, cfg["aa_depth"], float(cfg["agg_eps"]))
-    assert len(b) == 196, len(b)
-    return b + b"\0" * 60
+    return PK.pack_config(cfg, img_h=cfg["img"], img_w=cfg["img"], features=cfg["features"],
+                          out_channels=cfg["out_channels"], taps=cfg["taps"], metric=2, family=FAMILY_VGGT,
+                          frames=int(frames), npre=NPRE, aa_depth=cfg["aa_depth"], agg_eps=float(cfg["agg_eps"]))
 
 
 def pack_bytes(sd: Dict[str, np.ndarray], cfg: dict, frames: int = 1) -> bytes:

@@ -26,11 +26,12 @@ positive (a map that is mostly 0 is a weak parity signal).
 
 from __future__ import annotations
 
-import hashlib
 from collections import OrderedDict
 from typing import Dict, List, Tuple
 
 import numpy as np
+
+from .weights import Spec, draw, image_u8, spec_keys, spec_shapes, state_dict_digest  # noqa: F401
 
 LN_EPS = 1e-6
 HEAD_HIDDEN = 32   # HF DepthProDepthEstimationHead: Conv2d(features // 2, 32, 3)
@@ -66,7 +67,7 @@ def depth_pro_config(preset: str = "dinov2l16_384", use_fov: bool = True, **over
     return cfg
 
 
-def _vit_spec(pfx: str, cfg: dict) -> List[Tuple[str, Tuple[int, ...], str, float]]:
+def _vit_spec(pfx: str, cfg: dict) -> Spec:
     D, P = cfg["embed_dim"], cfg["patch"]
     G = cfg["vit_size"] // P
     e = pfx + "embeddings."
@@ -91,7 +92,7 @@ def _vit_spec(pfx: str, cfg: dict) -> List[Tuple[str, Tuple[int, ...], str, floa
     return s
 
 
-def _rcu_spec(pfx: str, F: int):
+def _rcu_spec(pfx: str, F: int) -> Spec:
     s = []
     for u in (1, 2):
         for c in (1, 2):
@@ -100,7 +101,7 @@ def _rcu_spec(pfx: str, F: int):
     return s
 
 
-def _spec(cfg: dict) -> List[Tuple[str, Tuple[int, ...], str, float]]:
+def _spec(cfg: dict) -> Spec:
     """(key, shape, kind, fan_in) in the fixed draw order of the RNG."""
     D, F = cfg["embed_dim"], cfg["fusion"]
     sd_, idims = cfg["scaled_dims"], cfg["inter_dims"]
@@ -164,47 +165,15 @@ def fov_final_kernel(cfg: dict) -> int:
 
 
 def synthetic_state_dict(cfg: dict, seed: int = 4321) -> "OrderedDict[str, np.ndarray]":
-    rng = np.random.Generator(np.random.PCG64(seed))
-    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
-    for key, shape, kind, fan_in in _spec(cfg):
-        if kind == "zero":
-            a = np.zeros(shape, np.float32)
-        else:
-            z = rng.standard_normal(shape, dtype=np.float32)
-            if kind == "w":
-                a = z * np.float32(1.0 / np.sqrt(fan_in))
-            elif kind == "b":
-                a = z * np.float32(0.02)
-            elif kind == "bpos":
-                a = np.float32(0.5) + z * np.float32(0.02)
-            elif kind == "g":
-                a = np.float32(1.0) + z * np.float32(0.1)
-            elif kind == "ls":
-                a = np.float32(0.5) + z * np.float32(0.05)
-            elif kind == "tok":
-                a = z * np.float32(0.5)
-            else:  # pragma: no cover
-                raise AssertionError(kind)
-        out[key] = np.ascontiguousarray(a, dtype=np.float32)
-    return out
+    return draw(_spec(cfg), seed)
 
 
 def expected_keys(cfg: dict) -> List[str]:
-    return [k for k, *_ in _spec(cfg)]
+    return spec_keys(_spec(cfg))
 
 
 def expected_shapes(cfg: dict) -> Dict[str, Tuple[int, ...]]:
-    return {k: tuple(s) for k, s, *_ in _spec(cfg)}
-
-
-def state_dict_digest(sd: Dict[str, np.ndarray]) -> str:
-    h = hashlib.sha256()
-    for k in sorted(sd):
-        a = np.ascontiguousarray(np.asarray(sd[k], dtype=np.float32))
-        h.update(k.encode())
-        h.update(str(a.shape).encode())
-        h.update(a.tobytes())
-    return h.hexdigest()
+    return spec_shapes(_spec(cfg))
 
 
 def synthetic_images(batch: int, size: int = 1536, first_seed: int = 0) -> np.ndarray:
@@ -213,7 +182,6 @@ def synthetic_images(batch: int, size: int = 1536, first_seed: int = 0) -> np.nd
     Normalize([0.5]*3, [0.5]*3)) -> float32 NCHW [batch, 3, size, size]."""
     out = np.empty((batch, 3, size, size), np.float32)
     for i in range(batch):
-        rng = np.random.Generator(np.random.PCG64(first_seed + i))
-        u = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
+        u = image_u8(first_seed + i, size, size)
         out[i] = ((u.astype(np.float32) / np.float32(255.0) - np.float32(0.5)) / np.float32(0.5)).transpose(2, 0, 1)
     return out

@@ -37,11 +37,13 @@ LayerNorm gamma 1 +- 0.1, biases N(0, 0.02^2), tokens N(0, 0.5^2).
 
 from __future__ import annotations
 
-import hashlib
 from collections import OrderedDict
 from typing import Dict, List, Tuple
 
 import numpy as np
+
+from .weights import (Spec, block_spec, dpt_head_spec, draw, image_u8, spec_keys, spec_shapes,  # noqa: F401
+                      state_dict_digest)
 
 PATCH = 14
 NUM_REG = 4            # DINOv2 register tokens == aggregator register tokens
@@ -80,113 +82,36 @@ def vggt_config(preset: str = "vggt_1b", **over) -> dict:
     return cfg
 
 
-def _block(s, b: str, D: int, qk_norm: bool):
-    s += [(b + "norm1.weight", (D,), "g", 0), (b + "norm1.bias", (D,), "b", 0),
-          (b + "attn.qkv.weight", (3 * D, D), "w", D), (b + "attn.qkv.bias", (3 * D,), "b", 0)]
-    if qk_norm:
-        s += [(b + "attn.q_norm.weight", (64,), "g", 0), (b + "attn.q_norm.bias", (64,), "b", 0),
-              (b + "attn.k_norm.weight", (64,), "g", 0), (b + "attn.k_norm.bias", (64,), "b", 0)]
-    s += [(b + "attn.proj.weight", (D, D), "w", D), (b + "attn.proj.bias", (D,), "b", 0),
-          (b + "ls1.gamma", (D,), "ls", 0),
-          (b + "norm2.weight", (D,), "g", 0), (b + "norm2.bias", (D,), "b", 0),
-          (b + "mlp.fc1.weight", (4 * D, D), "w", D), (b + "mlp.fc1.bias", (4 * D,), "b", 0),
-          (b + "mlp.fc2.weight", (D, 4 * D), "w", 4 * D), (b + "mlp.fc2.bias", (D,), "b", 0),
-          (b + "ls2.gamma", (D,), "ls", 0)]
-
-
-def _spec(cfg: dict) -> List[Tuple[str, Tuple[int, ...], str, float]]:
-    """(key, shape, kind, fan_in) in a fixed order -- the draw order of the RNG."""
-    D, F, P = cfg["embed_dim"], cfg["features"], cfg["patch"]
-    oc = cfg["out_channels"]
+def _spec(cfg: dict) -> Spec:
+    D, P = cfg["embed_dim"], cfg["patch"]
     G = cfg["img"] // P
-    s: List[Tuple[str, Tuple[int, ...], str, float]] = []
     p = "aggregator.patch_embed."
-    s += [(p + "cls_token", (1, 1, D), "tok", 0), (p + "pos_embed", (1, 1 + G * G, D), "tok", 0),
-          (p + "register_tokens", (1, NUM_REG, D), "tok", 0), (p + "mask_token", (1, D), "zero", 0),
-          (p + "patch_embed.proj.weight", (D, 3, P, P), "w", 3 * P * P),
-          (p + "patch_embed.proj.bias", (D,), "b", 0)]
+    s = [(p + "cls_token", (1, 1, D), "tok", 0), (p + "pos_embed", (1, 1 + G * G, D), "tok", 0),
+         (p + "register_tokens", (1, NUM_REG, D), "tok", 0), (p + "mask_token", (1, D), "zero", 0),
+         (p + "patch_embed.proj.weight", (D, 3, P, P), "w", 3 * P * P),
+         (p + "patch_embed.proj.bias", (D,), "b", 0)]
     for i in range(cfg["depth"]):
-        _block(s, f"{p}blocks.{i}.", D, False)
+        s += block_spec(f"{p}blocks.{i}.", D)
     s += [(p + "norm.weight", (D,), "g", 0), (p + "norm.bias", (D,), "b", 0)]
     a = "aggregator."
     s += [(a + "camera_token", (1, 2, 1, D), "tok", 0), (a + "register_token", (1, 2, NUM_REG, D), "tok", 0)]
-    for i in range(cfg["aa_depth"]):
-        _block(s, f"{a}frame_blocks.{i}.", D, True)
-    for i in range(cfg["aa_depth"]):
-        _block(s, f"{a}global_blocks.{i}.", D, True)
-    h = "depth_head."
-    C2 = 2 * D
-    s += [(h + "norm.weight", (C2,), "g", 0), (h + "norm.bias", (C2,), "b", 0)]
-    for i in range(4):
-        s += [(f"{h}projects.{i}.weight", (oc[i], C2, 1, 1), "w", C2),
-              (f"{h}projects.{i}.bias", (oc[i],), "b", 0)]
-    s += [(h + "resize_layers.0.weight", (oc[0], oc[0], 4, 4), "w", oc[0]),
-          (h + "resize_layers.0.bias", (oc[0],), "b", 0),
-          (h + "resize_layers.1.weight", (oc[1], oc[1], 2, 2), "w", oc[1]),
-          (h + "resize_layers.1.bias", (oc[1],), "b", 0),
-          (h + "resize_layers.3.weight", (oc[3], oc[3], 3, 3), "w", 9 * oc[3]),
-          (h + "resize_layers.3.bias", (oc[3],), "b", 0)]
-    for i in range(4):
-        s += [(f"{h}scratch.layer{i + 1}_rn.weight", (F, oc[i], 3, 3), "w", 9 * oc[i])]
-    for r in range(1, 5):
-        rb = f"{h}scratch.refinenet{r}."
-        s += [(rb + "out_conv.weight", (F, F, 1, 1), "w", F), (rb + "out_conv.bias", (F,), "b", 0)]
-        for u in ((2,) if r == 4 else (1, 2)):   # refinenet4: has_residual=False
-            for c in (1, 2):
-                s += [(f"{rb}resConfUnit{u}.conv{c}.weight", (F, F, 3, 3), "w", 9 * F),
-                      (f"{rb}resConfUnit{u}.conv{c}.bias", (F,), "b", 0)]
-    H2 = cfg["head_hidden"]
-    s += [(h + "scratch.output_conv1.weight", (F // 2, F, 3, 3), "w", 9 * F),
-          (h + "scratch.output_conv1.bias", (F // 2,), "b", 0),
-          (h + "scratch.output_conv2.0.weight", (H2, F // 2, 3, 3), "w", 9 * (F // 2)),
-          (h + "scratch.output_conv2.0.bias", (H2,), "b", 0),
-          (h + "scratch.output_conv2.2.weight", (cfg["out_dim"], H2, 1, 1), "w", H2),
-          (h + "scratch.output_conv2.2.bias", (cfg["out_dim"],), "b", 0)]
-    return s
+    for kind in ("frame_blocks", "global_blocks"):
+        for i in range(cfg["aa_depth"]):
+            s += block_spec(f"{a}{kind}.{i}.", D, qk_norm=True)
+    return s + dpt_head_spec(cfg, 2 * D, out_dim=cfg["out_dim"], rf4_unit1=False, norm=True)
 
 
 def expected_keys(cfg: dict) -> List[str]:
-    return [k for k, *_ in _spec(cfg)]
+    return spec_keys(_spec(cfg))
 
 
 def expected_shapes(cfg: dict) -> Dict[str, Tuple[int, ...]]:
-    return {k: shape for k, shape, *_ in _spec(cfg)}
+    return spec_shapes(_spec(cfg))
 
 
 def synthetic_state_dict(cfg: dict, seed: int = 2468) -> "OrderedDict[str, np.ndarray]":
     """Seeded, fan-in scaled upstream-keyed state dict (float32 numpy)."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
-    for key, shape, kind, fan_in in _spec(cfg):
-        if kind == "zero":
-            a = np.zeros(shape, np.float32)
-        else:
-            a = rng.standard_normal(shape, dtype=np.float32)
-            if kind == "w":
-                a *= np.float32(1.0 / np.sqrt(fan_in))
-            elif kind == "b":
-                a *= np.float32(0.02)
-            elif kind == "g":
-                a = np.float32(1.0) + a * np.float32(0.1)
-            elif kind == "ls":
-                a = np.float32(0.5) + a * np.float32(0.05)
-            elif kind == "tok":
-                a *= np.float32(0.5)
-            else:  # pragma: no cover
-                raise AssertionError(kind)
-        out[key] = np.ascontiguousarray(a, dtype=np.float32)
-    return out
-
-
-def state_dict_digest(sd: Dict[str, np.ndarray]) -> str:
-    """sha256 over keys + raw float32 bytes, in key order."""
-    h = hashlib.sha256()
-    for k in sorted(sd):
-        a = np.ascontiguousarray(np.asarray(sd[k], dtype=np.float32))
-        h.update(k.encode())
-        h.update(str(a.shape).encode())
-        h.update(a.tobytes())
-    return h.hexdigest()
+    return draw(_spec(cfg), seed)
 
 
 def synthetic_images(batch: int, frames: int, size: int, first_seed: int = 0) -> np.ndarray:
@@ -196,7 +121,5 @@ def synthetic_images(batch: int, frames: int, size: int, first_seed: int = 0) ->
     out = np.empty((batch, frames, 3, size, size), np.float32)
     flat = out.reshape(batch * frames, 3, size, size)
     for i in range(batch * frames):
-        rng = np.random.Generator(np.random.PCG64(first_seed + i))
-        u = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
-        flat[i] = (u.astype(np.float64) / 255.0).transpose(2, 0, 1)
+        flat[i] = (image_u8(first_seed + i, size, size).astype(np.float64) / 255.0).transpose(2, 0, 1)
     return out
