@@ -412,6 +412,45 @@ int mde_op_dp_preprocess(const unsigned char* src, int batch, int sh, int sw, in
                          const float* lut256, float* dst_f32_nchw, int oh, int ow, void* stream);
 int mde_op_dp_postprocess(const float* inv, int batch, int ih, int iw, const float* fov_deg, float f_px,
                           float* f_px_out, float* depth, int oh, int ow, void* stream);
+/* Point clouds (added to ABI 11 without a new version number -- purely additive, and
+ * tests/test_depth_pro_photo_cpu.py pins mde_version() == 11; a caller that must know looks the symbol up):
+ * the tail of reference models/depth_pro/onnx2trt_pointcloud.py (:172-184),
+ * pinhole unprojection of metric depth into PLY binary_little_endian vertex records, on the device.
+ * depth is fp32 [batch][h][w] (the output of mde_op_dp_postprocess / mde_op_depth_postprocess); photo is
+ * optional, uint8 [batch][h][pitch] of the same h, w, 3 interleaved channels per pixel with the rules of
+ * mde_op_resize_u8 (pitch >= 3 * w, bytes of a row past 3 * w are never read, swap_rb != 0 writes source
+ * channel 2 - c to output channel c).  f_px_dev is a device float[batch] (the f_px_out of
+ * mde_op_dp_postprocess: no host round trip) and may be null; then the host floats fx, fy (> 0) hold for
+ * every image.  cx, cy are host floats (the reference uses w / 2, h / 2).  The contract:
+ *   sampled grid: hs = ceil(h / step) by ws = ceil(w / step), sample (i, j) is pixel
+ *                 (v, u) = (i * step, j * step), z = depth[b][v][u]
+ *   fx = fy = f_px_dev[b] when f_px_dev is given, else the host floats fx, fy
+ *   every operation float32 and rounded separately, never fused:
+ *     xn = ((float)u - cx) / fx          yn = ((float)v - cy) / fy        (IEEE division)
+ *     X = xn * z,  Y = yn * z,  Z = z
+ *   colour = photo bytes of pixel (v, u), output order R, G, B after swap_rb
+ *   record = float X, Y, Z, then uchar R, G, B when a photo is given: rec = 15 bytes (12 without),
+ *            tightly packed; image b's region starts at byte b * hs * ws * rec of `records`, whatever
+ *            alignment that and the base pointer have
+ *   organized (compact == 0): every sample is written, record index = sample index (row-major), no
+ *            range test, a NaN z gives NaN X, Y, Z; counts[b] = hs * ws; one kernel
+ *   compact: a sample is kept iff z == z && z >= z_lo && z <= z_hi (bounds inclusive; NaN, and +-inf
+ *            outside the range, are dropped); the kept records are dense, in row-major sample order;
+ *            counts[b] (device int32[batch]) = number kept; bytes of the region past counts[b] records
+ *            are not written; the same bytes on every run.  Three kernels (count per workgroup, scan,
+ *            write) that need ws, mde_op_point_cloud_ws_bytes(batch, h, w, step) bytes of device
+ *            scratch, 4-byte aligned (0 is returned for sizes the op refuses).
+ * The kernels are pinned bit for bit to monocular_depth_estimation_trt_amd/pointcloud.py:unproject_np.
+ * mde_op_point_cloud only enqueues on `stream` (no allocation, no synchronisation, no host read of
+ * counts: capturable).  MDE_ERR_ARG, before any device call: null depth, records or counts; a
+ * non-positive size or step; a photo with pitch < 3 * w; f_px_dev null and fx <= 0 or fy <= 0; NaN cx or
+ * cy; h * w or hs * ws of 2^31 - 256 or more; batch > 65535; records_bytes < batch * hs * ws * rec;
+ * compact with ws null or ws_bytes too small, or z_lo > z_hi. */
+size_t mde_op_point_cloud_ws_bytes(int batch, int h, int w, int step);
+int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, const unsigned char* photo, int pitch,
+                       int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
+                       float z_lo, float z_hi, void* records, size_t records_bytes, int* counts, void* ws,
+                       size_t ws_bytes, void* stream);
 /* Depth Pro pyramid patches (upstream DepthProEncoder._create_pyramid + _split, reference engine input
  * "input"): fp32 NCHW image [batch][3][size][size] (size = 4 * 384) -> f16 patch-embed rows
  * [nseq * batch * 576][768] ((c, py, px) order), sequence s = patch * batch + image with the 25

@@ -212,6 +212,15 @@ hipError_t launch_dp_preprocess(const unsigned char* src, int B, int sh, int sw,
                                 const float* lut, float* dst, int oh, int ow, hipStream_t st);
 hipError_t launch_dp_postprocess(const float* inv, int B, int ih, int iw, const float* fov_deg, float f_px,
                                  float* f_px_out, float* out, int oh, int ow, hipStream_t st);
+// point_cloud.hip: pinhole unprojection of fp32 depth [B][h][w] (every step-th pixel on both axes) into
+// packed PLY vertex records (float x, y, z [+ uchar r, g, b from photo [B][h][pitch]]), organized or
+// compacted to z in [z_lo, z_hi]; counts int[B]; ws = point_cloud_ws_bytes() of scratch (compact only).
+// Enqueues one (organized) or three (compact) kernels, nothing else.  No argument checks here: the ABI
+// wrapper in ops_abi.hip holds the only copy of the limits
+size_t point_cloud_ws_bytes(int B, int h, int w, int step);
+hipError_t launch_point_cloud(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
+                              int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
+                              float z_lo, float z_hi, void* records, int* counts, void* ws, hipStream_t st);
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H,
                              int W, int ph, int pw, int T, int D, hipStream_t st, h16* Xh = nullptr,
                              float* lnst = nullptr, const float* cls_st = nullptr, float* P32 = nullptr);

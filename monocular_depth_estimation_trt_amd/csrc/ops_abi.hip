@@ -95,6 +95,49 @@ int mde_op_dp_postprocess(const float* inv, int batch, int ih, int iw, const flo
          "mde_op_dp_postprocess");
 }
 
+namespace {
+// sampled grid of the point-cloud op; returns why it is unusable, else nullptr and the grid's size
+const char* point_cloud_geometry_error(int batch, int h, int w, int step, long long* plane) {
+  if (batch < 1 || h < 1 || w < 1) return "batch and sizes must be positive";
+  if (step < 1) return "step must be positive";
+  *plane = (long long)((h + (long long)step - 1) / step) * ((w + (long long)step - 1) / step);
+  if ((long long)h * w >= 0x7fffffffLL - 256 || *plane >= 0x7fffffffLL - 256)
+    return "a plane of 2^31 - 256 elements or more";
+  if (batch > 65535) return "batch > 65535";
+  return nullptr;
+}
+}  // namespace
+
+size_t mde_op_point_cloud_ws_bytes(int batch, int h, int w, int step) {
+  long long plane = 0;
+  if (point_cloud_geometry_error(batch, h, w, step, &plane)) return 0;
+  return point_cloud_ws_bytes(batch, h, w, step);
+}
+
+int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, const unsigned char* photo, int pitch,
+                       int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
+                       float z_lo, float z_hi, void* records, size_t records_bytes, int* counts, void* ws,
+                       size_t ws_bytes, void* st) {
+  long long plane = 0;
+  const char* why = (!depth || !records || !counts) ? "null pointer"
+                                                    : point_cloud_geometry_error(batch, h, w, step, &plane);
+  if (!why && photo && pitch < 3 * (long long)w) why = "pitch < 3 * w";
+  if (!why && !f_px_dev && !(fx > 0.f && fy > 0.f)) why = "f_px_dev is null and fx <= 0 or fy <= 0";
+  if (!why && !(cx == cx && cy == cy)) why = "cx or cy is NaN";
+  // batch <= 65535, plane < 2^31, rec <= 15: no overflow in 64 bits
+  if (!why && records_bytes < (unsigned long long)batch * plane * (photo ? 15 : 12))
+    why = "records_bytes < batch * hs * ws * record size";
+  if (!why && compact) {
+    if (!(z_lo <= z_hi)) why = "z_lo > z_hi (or NaN)";
+    else if (!ws || ws_bytes < point_cloud_ws_bytes(batch, h, w, step))
+      why = "compact mode needs ws of mde_op_point_cloud_ws_bytes()";
+  }
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_point_cloud: ") + why);
+  OP_RET(launch_point_cloud(depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy, compact, z_lo,
+                            z_hi, records, counts, ws, (hipStream_t)st),
+         "mde_op_point_cloud");
+}
+
 int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
   if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
   DpPyramid pyr;

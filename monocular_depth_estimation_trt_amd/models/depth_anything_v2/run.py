@@ -12,6 +12,7 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
         [--source synthetic:vits:metric | ckpt.pth] [--input x.npy] [--src-hw H W]
         [--image photo.npy|photo.jpg] [--host-preprocess]
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
+        [--ply out.ply --f-px F [--ply-step N]]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed -- taken through the
@@ -27,6 +28,16 @@ uint8 engine takes (core/onnx_tools.py:87-219: normalisation on the device);
 without it a synthetic image of the spec's input domain is used.  The
 post-process runs on the device (postprocess.DevicePostprocess) unless
 `--host-postprocess` asks for the reference's torch-CPU version.
+
+`--ply PATH` writes the point cloud of the metric depth map at the source size
+(the reference's models/depth_pro/onnx2trt_pointcloud.py:172-184 tail, which
+its docs/model_contracts.md allows for every "metric depth + focal length"
+model), on the device (pointcloud.DevicePointCloud) from the map the device
+post-process left there, coloured from the `--image` photo, depths outside this
+driver's clamp [1e-3, 1e3] dropped.  There is no FOV head: `--f-px` (focal
+length in pixels at the source size) is required.  Relative models (the
+relative checkpoints, depth_anything_ac, distill_any_depth) are refused:
+relative depth is not turned into metres.
 """
 
 import argparse
@@ -36,6 +47,7 @@ import time
 import numpy as np
 
 from monocular_depth_estimation_trt_amd import bench, common, spec, weights
+from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
                                                            resize_linear_u8)
@@ -72,7 +84,28 @@ def build_parser(model="depth_anything_v2", mc=None):
     ap.add_argument("--out-dir", default=os.path.join(os.getcwd(), "reports", "bench"))
     ap.add_argument("--input-format", choices=("float32_nchw", "uint8_nhwc"), default="float32_nchw")
     ap.add_argument("--host-postprocess", action="store_true")
+    ap.add_argument("--ply", default="", metavar="PATH",
+                    help="write the point cloud (binary PLY; colours from --image) of the metric depth; needs --f-px")
+    ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
+    ap.add_argument("--f-px", type=float, default=None, help="with --ply: focal length in pixels at the source size")
     return ap
+
+
+NOT_METRIC = "--ply needs a metric model: relative depth is not turned into metres"
+
+
+def _check_ply(a, mc):
+    """--ply's conditions that can be answered before an engine is built."""
+    if a.f_px is None or not a.f_px > 0:
+        raise SystemExit("--ply needs --f-px (a positive focal length in pixels): this model predicts none")
+    if a.ply_step < 1:
+        raise SystemExit("--ply-step must be positive")
+    fields = a.source.split(":")
+    if mc["depth_type"] != "metric" or (fields[0] == "synthetic" and len(fields) > 2 and fields[2] == "relative"):
+        raise SystemExit(NOT_METRIC)
+    if a.host_postprocess or mc["postprocess"] == "none":
+        raise SystemExit("--ply runs on the device post-process's depth map: not with --host-postprocess or a model "
+                         "without a post-process")
 
 
 def _device_preprocess(img, model, input_hw, input_format, mem, stream):
@@ -108,9 +141,13 @@ def main(argv=None, model="depth_anything_v2"):
         raise SystemExit("--image and --input are exclusive")
     if a.host_preprocess and not a.image:
         raise SystemExit("--host-preprocess needs --image")
+    if a.ply:
+        _check_ply(a, mc)
     img = load_image_bgr(a.image) if a.image else None
     if a.src_hw is None:
         a.src_hw = list(img.shape[:2]) if img is not None else [2268, 3024]
+    if a.ply and img is not None and tuple(a.src_hw) != img.shape[:2]:
+        raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
     if u8 and a.engine.endswith("_fp16.mdeng"):
         a.engine = a.engine[:-len("_fp16.mdeng")] + "_u8_fp16.mdeng"
     if img is not None and a.host_preprocess:
@@ -132,6 +169,8 @@ def main(argv=None, model="depth_anything_v2"):
                            max_depth=mc["max_depth"], input_hw=(input_h, input_w),
                            input_format=a.input_format) as engine, \
             engine.create_execution_context() as context:
+        if a.ply and not engine.info.metric:
+            raise SystemExit(NOT_METRIC)
         inputs, outputs, bindings, stream = allocate_buffers(engine, output_shape, profile_idx=0)
         if x is None:
             ms = _device_preprocess(img, model, (input_h, input_w), a.input_format, inputs[0], stream)
@@ -151,6 +190,11 @@ def main(argv=None, model="depth_anything_v2"):
         else:  # the engine's output is still in outputs[0].device
             with DevicePostprocess(1, input_h, input_w, *a.src_hw) as pp:
                 depth = pp.run(outputs[0].device, stream)[0].copy()
+                if a.ply:  # the clamped map is still in pp.mem.device
+                    ms, n = device_ply(a.ply, pp.mem.device, *a.src_hw, stream, step=a.ply_step, img_bgr=img,
+                                       f_px=a.f_px, z_lo=1e-3, z_hi=1e3)
+                    print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {a.src_hw[0]}x{a.src_hw[1]} step "
+                          f"{a.ply_step} -> {a.ply} : {ms:0.3f} ms, {n} points")
         bench.record(model, samples, warmup=a.warmup, precision="fp16", profile="bench",
                      variant="u8" if u8 else "single",
                      input_h=input_h, input_w=input_w, engine_path=a.engine, outputs={"depth": depth},

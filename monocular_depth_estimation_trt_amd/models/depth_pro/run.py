@@ -11,6 +11,7 @@
     python -m monocular_depth_estimation_trt_amd.models.depth_pro.run \
         [--source synthetic:depth_pro | DepthPro.safetensors] [--image photo.npy|photo.jpg]
         [--input x.npy] [--src-hw H W] [--f-px F] [--host-preprocess] [--host-postprocess]
+        [--ply out.ply] [--ply-step N]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed.  It is normalised and
@@ -26,6 +27,14 @@ stream (postprocess.DepthProDevicePostprocess) and downloads the metric depth
 at the source size; `--host-postprocess` downloads the 1536^2 map and runs the
 reference's torch-CPU version.  `--f-px` is the reference's f_px0: a known
 focal length in pixels instead of the predicted one.
+
+`--ply PATH` is the reference's `onnx2trt_pointcloud.py:172-184`: the metric
+depth at the source size is unprojected with the focal length (x = (u - W/2) /
+f_px * z, y likewise) and written as a binary PLY, coloured from the `--image`
+photo (no colours with `--input` or the synthetic image).  It runs on the
+device (pointcloud.DevicePointCloud) on the depth map and the focal length the
+device post-process left there, drops depths outside [1e-4, 1e4] and downloads
+the PLY records; `--ply-step N` keeps every N-th pixel on both axes.
 """
 
 import argparse
@@ -38,6 +47,7 @@ import numpy as np
 from monocular_depth_estimation_trt_amd import bench, common, spec, weights_depth_pro
 from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
                                                                stream_synchronize)
+from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DepthProDevicePostprocess, depth_pro_postprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DepthProPreprocess, load_image_bgr,
                                                            preprocess_depth_pro_host)
@@ -71,6 +81,9 @@ def build_parser(model="depth_pro", size=None):
                     help="focal length in pixels (the reference's f_px0) instead of the predicted one")
     ap.add_argument("--src-hw", type=int, nargs=2, default=None,
                     help="source image size for the post-process (default: the image's / input's own size)")
+    ap.add_argument("--ply", default="", metavar="PATH",
+                    help="write the point cloud (binary PLY; colours from --image) of the metric depth")
+    ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out-dir", default=os.path.join(os.getcwd(), "reports", "bench"))
@@ -118,9 +131,12 @@ def _device_preprocess(img, size, mem, stream):
         ev.free()
 
 
-def _device_postprocess(outputs, size, src_hw, f_px, stream):
+def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None):
     """DepthProDevicePostprocess on the output bindings in place, timed with
-    hipEvents (kernel + D2H of the depth map and the focal length)."""
+    hipEvents (kernel + D2H of the depth map and the focal length); `ply` =
+    (path, step, photo or None): then the point cloud of the map, while it is
+    still on the device, with the focal length the post-process used (the
+    fourth result, pointcloud.device_ply's; else None)."""
     if f_px is None and len(outputs) < 2:
         raise SystemExit("this engine has no fov_deg output: pass --f-px")
     ev = _Events(stream)
@@ -131,7 +147,13 @@ def _device_postprocess(outputs, size, src_hw, f_px, stream):
             ev.mark(1)
             stream_synchronize(stream)
             depth, f = pp.result()
-            return depth[0].copy(), float(f[0]), ev.ms()
+            depth, f, ms = depth[0].copy(), float(f[0]), ev.ms()
+            cloud = None
+            if ply:
+                path, step, img = ply
+                cloud = device_ply(path, pp.mem.device, *src_hw, stream, step=step, img_bgr=img,
+                                   d_f_px=pp.f_px.device, f_px=f_px, z_lo=1e-4, z_hi=1e4)
+            return depth, f, ms, cloud
     finally:
         ev.free()
 
@@ -146,6 +168,11 @@ def main(argv=None, model="depth_pro"):
         raise SystemExit("--host-preprocess needs --image")
     if a.f_px is not None and not a.f_px > 0:
         raise SystemExit("--f-px must be positive")
+    if a.ply and a.host_postprocess:
+        raise SystemExit("--ply runs on the device post-process's depth map: do not combine it with "
+                         "--host-postprocess")
+    if a.ply and a.ply_step < 1:
+        raise SystemExit("--ply-step must be positive")
     img = load_image_bgr(a.image) if a.image else None
     if img is not None and not a.host_preprocess:
         x = None  # filled on the device, below
@@ -163,6 +190,8 @@ def main(argv=None, model="depth_pro"):
             how = "host, torch resize of a normalised tensor"
         print(f"[MDET] preprocess ({how}) {H}x{W} -> {size}x{size} : {(time.perf_counter() - t0) * 1e3:0.3f} ms")
     src_hw = tuple(a.src_hw) if a.src_hw else (H, W)
+    if a.ply and img is not None and src_hw != img.shape[:2]:
+        raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
     output_shapes = (1, 1, size, size)
     with common.get_engine(a.source, a.engine, "fp16", None, input_hw=(size, size)) as engine, \
             engine.create_execution_context() as context:
@@ -184,9 +213,13 @@ def main(argv=None, model="depth_pro"):
             print(f"[MDET] postprocess (host, torch) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{(time.perf_counter() - t0) * 1e3:0.3f} ms")
         else:  # the engine's outputs are still in outputs[*].device
-            depth, f_px, ms = _device_postprocess(outputs, size, src_hw, a.f_px, stream)
+            depth, f_px, ms, cloud = _device_postprocess(outputs, size, src_hw, a.f_px, stream,
+                                                         ply=(a.ply, a.ply_step, img) if a.ply else None)
             print(f"[MDET] postprocess (device, kernel + D2H, hipEvents) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{ms:0.3f} ms")
+            if cloud:
+                print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {src_hw[0]}x{src_hw[1]} step "
+                      f"{a.ply_step} -> {a.ply} : {cloud[0]:0.3f} ms, {cloud[1]} points")
         bench.record(model, samples, encoder="fixed", warmup=a.warmup, precision="fp16", profile="native",
                      input_h=size, input_w=size, engine_path=a.engine, outputs={"depth": depth, "f_px": np.array(f_px)},
                      notes=f"source={a.source}; 1536x1536 is upstream fixed", model_input=x, out_dir=a.out_dir)
