@@ -67,6 +67,18 @@ constexpr int PLDS = PTAB + 2 * PNMAX * 4;  // 156 KB at 3 slots (108 KB at 2)
 static_assert(PLDS <= 163840, "LDS");
 // (round 6: the GELU on scalar registers instead of packed f32 pairs spilled
 // 41 VGPRs in the LN-fold fc1 and ran slower; the packed form stays)
+#ifndef PX_STREAM
+// 1: a panel's A fragments stream in under its first unit -- that unit,
+// peeled off the loop, waits for fragment pair s at its k-substep s -- and
+// the previous panel's last epilogue no longer stands alone in front of the
+// drained load: E_STORE runs it inside the new panel's first unit, E_QKV
+// behind the new panel's loads (XPEEL in the kernel).  0: epilogue, panel
+// load, vmcnt(0), then the first unit (the form up to round 6; kept for the
+// A/B and the trace of it; 2: E_QKV's form in every kernel).  Bit-identical
+// either way.  In-kernel trace, fc1 B = 48 alone (profiles/panel_switch_trace.txt):
+// a switch costs the workgroup 9.8 us in form 0, 6.8 us in form 1.
+#define PX_STREAM 1
+#endif
 #ifndef PEPI_STRIDE
 #define PEPI_STRIDE 1  // k-substeps between the epilogue's block pairs
 #endif
@@ -126,21 +138,33 @@ __device__ __attribute__((aligned(16))) f16x4 g_psink[64];
 __device__ __attribute__((aligned(16))) uint4 g_psink8[64];  // (panel32's 16-B stores)
 
 #ifdef PX_TRACE
-// timing build only (tools/panel_trace.py): per (block < 8, wave, unit <
-// 96) the s_memtime after the unit's barrier and before its end-of-unit wait
-// (slot 3: s_memrealtime, 100 MHz, at the unit start -- the clock check)
+// timing build only (tools/panel_trace.py): per (traced workgroup < 8, wave,
+// unit < 96) the s_memtime after the unit's barrier and before its end-of-unit
+// wait (slot 3: s_memrealtime, 100 MHz, at the unit start -- the clock check).
+// Traced: workgroups 16 + 33 i (one per XCD, spread over a 256-workgroup
+// grid): with the even partition workgroups 0-7 of the B = 48 launches start
+// on a panel boundary and never switch panels; these switch after 23, 20, ..
+// 1 units.  Rows 90-95 hold the whole-kernel phases: 95 entry, 91 / 92 the
+// first panel's loads issued / waited for (the first MFMA is unit 0's slot
+// 0), 93 the last panel switch (slot 0 after the previous unit's end-of-unit
+// wait, 1 after its standalone epilogue, 2 when the switch's waits are done),
+// 94 slot 0 the local unit index that switch came before, 90 the end.
 __device__ unsigned long long g_ptrace[8][8][96][4];
+#define PTRACE_ON (blockIdx.x >= 16 && (blockIdx.x - 16) % 33 == 0 && (blockIdx.x - 16) / 33 < 8)
 #define PTRACE(SG, K)                                                     \
-  if (blockIdx.x < 8 && (SG) >= 0 && (SG) < 96) {                         \
+  if (PTRACE_ON && (SG) >= 0 && (SG) < 96) {                              \
     const unsigned long long tt = __builtin_amdgcn_s_memtime();           \
-    if (lane == 0) g_ptrace[blockIdx.x][wave][(SG)][(K)] = tt;            \
+    if (lane == 0) g_ptrace[(blockIdx.x - 16) / 33][wave][(SG)][(K)] = tt; \
     if ((K) == 0) {                                                       \
       const unsigned long long rt = __builtin_amdgcn_s_memrealtime();     \
-      if (lane == 0) g_ptrace[blockIdx.x][wave][(SG)][3] = rt;            \
+      if (lane == 0) g_ptrace[(blockIdx.x - 16) / 33][wave][(SG)][3] = rt; \
     }                                                                     \
   }
+#define PTRACE_VAL(SG, K, V) \
+  if (PTRACE_ON && lane == 0) g_ptrace[(blockIdx.x - 16) / 33][wave][(SG)][(K)] = (unsigned long long)(V);
 #else
 #define PTRACE(SG, K)
+#define PTRACE_VAL(SG, K, V)
 #endif
 
 template <int EM, int ACT, bool FOLD>
@@ -152,6 +176,15 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, hq = lane >> 4;
+  // (the f16-residual form keeps the drained panel load: streamed, its peeled
+  // unit spilled inside the MFMA stream, and it is not on a default path)
+  constexpr bool STREAM = PX_STREAM && EM != E_RESID;
+  // how a streamed run's first unit treats the previous panel's last epilogue:
+  // 2 = inside that unit, like any other (E_STORE); 1 = standalone in front of
+  // it, behind the new panel's loads (E_QKV: with the second panel's row
+  // addressing live beside the first's, its unit bodies spilled inside the
+  // MFMA stream); 0 = not streamed
+  constexpr int XPEEL = !STREAM ? 0 : (EM == E_STORE && PX_STREAM != 2 ? 2 : 1);  // (PX_STREAM 2: form 1 everywhere)
   // the workgroup's units (panel-major (panel, chunk) pairs): q = npan / G
   // whole panels first -- each panel's A is loaded by one workgroup, once --
   // then the leftover panels' units spread evenly over all workgroups as a
@@ -176,10 +209,27 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
 
   // per-column bias and folded-LN column sums, read by every epilogue
   // (E_RESID: tab_c holds the layer scale instead)
-  for (int i = tid; i < p.N; i += 512) {
-    tab_b[i] = p.bias ? p.bias[i] : 0.f;
-    tab_c[i] = FOLD ? p.lnc1[i] : (EM == E_RESID ? p.ls[i] : 0.f);
+  // Streamed forms: all the values are loaded here at once and stored behind
+  // the issue of the first chunks (one memory round trip, shared with those
+  // chunks, instead of one per 512 columns in front of them); the first
+  // unit's barrier orders the stores before any epilogue.
+  PTRACE(95, 0)  // (trace builds: kernel entry)
+  constexpr int PTPT = PNMAX / 512;  // table entries per thread
+  float tbv[PTPT], tcv[PTPT];
+#pragma unroll
+  for (int r = 0; r < PTPT; ++r) {
+    const int i = tid + 512 * r;
+    tbv[r] = (i < p.N && p.bias) ? p.bias[i] : 0.f;
+    tcv[r] = i < p.N ? (FOLD ? p.lnc1[i] : (EM == E_RESID ? p.ls[i] : 0.f)) : 0.f;
   }
+  auto tab_store = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int r = 0; r < PTPT; ++r) {
+      const int i = tid + 512 * r;
+      if (i < p.N) tab_b[i] = tbv[r], tab_c[i] = tcv[r];
+    }
+  };
+  if constexpr (!STREAM) tab_store();
 
   // ---- W chunk DMA: wave w fills rows 8w .. 8w + 7 of every 128-B row
   // segment; lane -> (row lane >> 3, physical chunk lane & 7) fetches logical
@@ -200,29 +250,49 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
   f16x8 af[2][PKS];
   auto row_of = [&](int pnl, int ib) __attribute__((always_inline)) { return pnl * PBM + wave * 32 + ib * 16 + l15; };
   auto load_panel = [&](int pnl) __attribute__((always_inline)) {
+    const f16* src[2];
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib) {
       const int m = row_of(pnl, ib);
-      const f16* src = reinterpret_cast<const f16*>(p.A) + (size_t)(m < p.M ? m : p.M - 1) * p.lda + 8 * hq;
+      src[ib] = reinterpret_cast<const f16*>(p.A) + (size_t)(m < p.M ? m : p.M - 1) * p.lda + 8 * hq;
+    }
+    if constexpr (STREAM) {
+      // in k-substep order: the panel's first unit waits for fragment pair s
+      // only at its substep s (vmcnt completes in order)
 #pragma unroll
-      for (int s = 0; s < PKS; ++s) af[ib][s] = *reinterpret_cast<const f16x8*>(src + 32 * s);
+      for (int s = 0; s < PKS; ++s)
+#pragma unroll
+        for (int ib = 0; ib < 2; ++ib) af[ib][s] = *reinterpret_cast<const f16x8*>(src[ib] + 32 * s);
+    } else {
+#pragma unroll
+      for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+        for (int s = 0; s < PKS; ++s) af[ib][s] = *reinterpret_cast<const f16x8*>(src[ib] + 32 * s);
     }
   };
   // folded LayerNorm: (mean, rstd) of the lane's two rows from the
   // producers' 32-column slice partials, merged as the 128^2 kernel does
   // (ln_merge_stats): the 4 lanes of a row take slices q, q + 4, ..
-  auto panel_stats = [&](int pnl, float (&mean_o)[2], float (&rstd_o)[2]) __attribute__((always_inline)) {
+  // (the loads and the merge apart: the streamed switch runs the previous
+  // panel's last epilogue, with that panel's statistics, between them)
+  // lnst_ns = K / 32 = 12 slices (panel_gemm_eligible), so a lane holds
+  // LKP = 3 of them: 6 loads and 12 registers per panel, the rest of t zero
+  // (ln_merge_stats adds 0 for k >= kp whatever t holds there)
+  constexpr int LKP = PK / 32 / 4;
+  auto stats_load = [&](int pnl, float2 (&t)[2][8]) __attribute__((always_inline)) {
     const float2* st2 = reinterpret_cast<const float2*>(p.lnst_in) + (unsigned)(hq * p.lnst_rows);
-    const int kp = p.lnst_ns >> 2;
-    const float invd = 1.f / (float)(p.lnst_ns * 32);  // as gemm.hip computes it (device division)
-    float2 t[2][8];
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib) {
       const int m = row_of(pnl, ib);
       const int mr = m < p.M ? m : p.M - 1;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) t[ib][k] = st2[(unsigned)((k < kp ? 4 * k : 0) * p.lnst_rows + mr)];
+      for (int k = 0; k < 8; ++k)
+        t[ib][k] = k < LKP ? st2[(unsigned)(4 * k * p.lnst_rows + mr)] : float2{0.f, 0.f};
     }
+  };
+  auto stats_merge = [&](const float2 (&t)[2][8], float (&mean_o)[2], float (&rstd_o)[2]) __attribute__((always_inline)) {
+    constexpr int kp = LKP;
+    const float invd = 1.f / (float)(p.lnst_ns * 32);  // as gemm.hip computes it (device division)
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib) {
       float var;
@@ -410,9 +480,17 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
   // hoisting all 48 fragment reads (192 VGPRs) and keeps each epilogue block
   // beside its substep's 8 MFMAs.
   const int cx = (hq ^ (lane & 7)) << 4;  // physical chunk of logical chunk hq in rows r (r & 7 = lane & 7)
-  auto unit = [&](auto off_tag, int slot, f32x4(&accC)[2][4], const f32x4(&accP)[2][4], bool epi, int ppnl, int pc,
-                  const float (&pmean)[2], const float (&prstd)[2], int cpnl, int cc) __attribute__((always_inline)) {
+  // peel_tag (the streamed forms' first unit of a run; 0 elsewhere):
+  //  2 -- the epilogue is the PREVIOUS panel's last one (ppnl, its
+  //       statistics), and once its last block pair is done this panel's
+  //       LayerNorm statistics loads are issued into lst -- the accumulator
+  //       set just read out is dead by then;
+  //  1 -- no epilogue at all: the previous panel's last one ran standalone
+  auto unit = [&](auto off_tag, auto peel_tag, int slot, f32x4(&accC)[2][4], const f32x4(&accP)[2][4], bool epi, int ppnl, int pc,
+                  const float (&pmean)[2], const float (&prstd)[2], int cpnl, int cc, float2 (&lst)[2][8])
+                  __attribute__((always_inline)) {
     constexpr int OFF = decltype(off_tag)::value;
+    constexpr int PEEL = decltype(peel_tag)::value;
     const char* sw = smem + slot * PCHB + l15 * 128;
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib)
@@ -440,7 +518,7 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
       const bool ep = s >= OFF && ((s - OFF) % E) == 0 && (s - OFF) / E < 4;
       const int q = (s - OFF) / E;
       ColB cb[2];
-      if (ep) cb[0] = col_read(pc, (2 * q) & 3), cb[1] = col_read(pc, (2 * q + 1) & 3);
+      if (PEEL != 1 && ep) cb[0] = col_read(pc, (2 * q) & 3), cb[1] = col_read(pc, (2 * q + 1) & 3);
 #pragma unroll
       for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
@@ -448,10 +526,13 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
       // blocks 2s, 2s + 1 of the previous unit in substeps 0 .. 3: its stores
       // are then at least 8 substeps old at the end-of-unit wait
       if (ep) {
-        epi_pair(2 * q, ppnl, pc, accP, pmean, prstd, cb, epi);
+        if constexpr (PEEL != 1) epi_pair(2 * q, ppnl, pc, accP, pmean, prstd, cb, epi);
         // (E_RESID) those two blocks' registers now take this unit's
         // residual values -- landed by the end-of-unit wait, used next unit
         res_load2(2 * q, cpnl, cc);
+        if constexpr (PEEL == 2 && FOLD) {
+          if (q == 3) stats_load(cpnl, lst);
+        }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -471,6 +552,7 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
 #pragma unroll
   for (int r = 0; r < PLEAD; ++r)
     if (r < nu) issue(r);
+  if constexpr (STREAM) tab_store();
   // ---- the unit loop, one copy per epilogue placement: the two waves of a
   // SIMD (w, w + 4) run their epilogue VALU in different k-substeps, so one's
   // VALU-heavy substeps meet the other's MFMA-only ones (the same substeps
@@ -499,12 +581,72 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
       const int gu = gunit(j), pnl = gu / nch;
       // the run: this panel's units inside the current (main or tail) range
       const int jend = min(j < nm ? nm : nu, j + (pnl + 1) * nch - gu);
-      // the previous panel's last epilogue runs here, on its own (once per
-      // panel switch): the stats registers then hold one panel at a time
-      if (j > 0) epi_all(acc1);
-      load_panel(pnl);
-      if constexpr (FOLD) panel_stats(pnl, lmean, lrstd);
-      pwait_vm0();  // A and every issued chunk landed (once per panel)
+      if (j > 0) {
+        PTRACE(93, 0)
+        PTRACE_VAL(94, 0, j)
+      } else {
+        PTRACE(91, 0)
+      }
+      float2 lst[2][8];  // the panel's LN statistics partials between their loads and the merge
+      if constexpr (XPEEL == 2) {
+        // a switch is the new panel's 24 A loads (substep order) and nothing
+        // else: the previous panel's last epilogue runs inside the new panel's
+        // first unit like any other (af is dead after a panel's last unit, so
+        // the loads can be issued here; lmean / lrstd keep the previous
+        // panel's statistics through that unit, which loads the new ones once
+        // its epilogue is done and merges them at its end).  Waits, all by
+        // count (vmcnt completes in order):
+        //  * kernel start (j = 0): vmcnt(24) -- everything older than the A
+        //    loads, i.e. the prologue's chunks 0 .. PLEAD - 1 (the first two
+        //    units' W);
+        //  * a switch (j > 0): no chunk wait -- chunk j landed by unit j - 1's
+        //    end-of-unit wait, chunk j + 1's is unit j's own (below);
+        //  * the A fragments: plain loads, so the compiler's wait insertion puts
+        //    vmcnt(24 - 2 (s + 1) + the unit's stores so far) in front of the
+        //    first unit's substep s.  The chunk DMA issued at the top of that
+        //    unit (6 operations the compiler does not see) is newer than every A
+        //    load, so that count is strict by up to three substeps, never lax.
+        load_panel(pnl);
+        if (j == 0) {
+          pwait_vm<2 * PKS>();
+        } else {
+          PTRACE(93, 1)  // (no standalone epilogue in this form)
+        }
+      } else if constexpr (XPEEL == 1) {
+        // the new panel's loads first -- the statistics, then the 24 A
+        // fragments -- and the previous panel's last epilogue standalone
+        // behind them (lmean / lrstd hold that panel's statistics until the
+        // merge below).  Waits as above; the merge reads the statistics, the
+        // oldest of these loads: the compiler's own count for them leaves the
+        // A loads and the epilogue's stores out
+        if constexpr (FOLD) stats_load(pnl, lst);
+        load_panel(pnl);
+        if (j > 0) {
+          epi_all(acc1);
+          PTRACE(93, 1)
+        } else {
+          pwait_vm<2 * PKS>();
+        }
+        if constexpr (FOLD) stats_merge(lst, lmean, lrstd);
+      } else {
+        // the previous panel's last epilogue runs here, on its own (once per
+        // panel switch): the stats registers then hold one panel at a time
+        if (j > 0) {
+          epi_all(acc1);
+          PTRACE(93, 1)
+        }
+        load_panel(pnl);
+        if constexpr (FOLD) {
+          stats_load(pnl, lst);
+          stats_merge(lst, lmean, lrstd);
+        }
+        pwait_vm0();  // A and every issued chunk landed (once per panel)
+      }
+      if (j > 0) {
+        PTRACE(93, 2)
+      } else {
+        PTRACE(92, 0)
+      }
       const int j0 = j;
       // one unit: chunk jj visible to all waves after the barrier, and slot
       // (jj + PLEAD) % PSLOTS (unit jj - 1's) read by all, so chunk jj + PLEAD
@@ -513,36 +655,86 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
       // 8 vector-memory ops after it (the epilogue's stores; E_QKV's V^T
       // chunks 32), so vmcnt(8 PLEAD) waits for it and leaves the newer chunk
       // DMAs and this unit's stores in flight (an older store waited for too
-      // is long done)
-      auto step = [&](int jj, f32x4(&accC)[2][4], const f32x4(&accP)[2][4]) __attribute__((always_inline)) {
+      // is long done).
+      // Streamed forms, a run's first unit j0: chunk j0 + 1 was issued at the
+      // top of unit j0 - 1, and that unit's 8 stores and the switch's 24 A
+      // loads are newer: vmcnt(16) holds (at j0 = 0 chunk 1 landed by the
+      // vmcnt(24) in front of the run).
+      //  * peel 2: the unit stores like any other, so every count is the
+      //    general one; with the LN fold it ends on the merge of the
+      //    statistics it loaded after its last stores, the newest operations
+      //    the compiler counts, so its wait for them has drained the rest;
+      //  * peel 1: the unit has no epilogue and issues NO stores, so for unit
+      //    j0 + 1 -- chunk j0 + 2 was issued at the top of unit j0 -- only that
+      //    unit's own 6 chunk DMAs, if it issued any, and its 8 stores are
+      //    newer: vmcnt(14) / vmcnt(8).  Every later unit has a predecessor
+      //    with 8 stores: vmcnt(16).
+      auto step = [&](auto peel_tag, int jj, f32x4(&accC)[2][4], const f32x4(&accP)[2][4]) __attribute__((always_inline)) {
+        constexpr int PEEL = decltype(peel_tag)::value;
         pbarrier();
         PTRACE(jj, 0)
         if (jj + PLEAD < nu) issue(jj + PLEAD);
         const int cc = gunit(jj) - pnl * nch;
-        unit(off_tag, jj % PSLOTS, accC, accP, jj > j0, pnl, pc, lmean, lrstd, pnl, cc);
+        // (peel 2: the epilogue is the previous panel's last unit's -- none at
+        // the kernel start, where it computes into the sink as before)
+        unit(off_tag, peel_tag, jj % PSLOTS, accC, accP, PEEL == 2 ? j0 > 0 : (STREAM ? true : jj > j0),
+             PEEL == 2 ? ppnl : pnl, pc, lmean, lrstd, pnl, cc, lst);
+        if constexpr (PEEL == 2 && FOLD) stats_merge(lst, lmean, lrstd);
         ppnl = pnl;
         pc = cc;
         PTRACE(jj, 1)
-        if constexpr (EM == E_RESID) pwait_vm0();  // (its residual loads: consumed next unit)
-        else pwait_vm<8 * PLEAD>();
+        static_assert(!STREAM || PLEAD == 2, "streamed forms: the counts assume a 3-slot ring");
+        if constexpr (EM == E_RESID) {
+          pwait_vm0();  // (its residual loads: consumed next unit)
+        } else if (XPEEL == 1 && jj == j0 + 1) {
+          if (jj + PLEAD < nu) pwait_vm<6 + 8>();
+          else pwait_vm<8>();
+        } else {
+          pwait_vm<8 * PLEAD>();
+        }
         PTRACE(jj, 2)
       };
+      const std::integral_constant<int, 0> in_run{};
       // two units per iteration with the accumulator roles swapped: no copy
       // of the 32 accumulator registers per unit
-      for (; j + 1 < jend; j += 2) {
-        step(j, acc0, acc1);
-        step(j + 1, acc1, acc0);
-      }
-      if (j < jend) {
-        step(j, acc0, acc1);
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-          for (int jb = 0; jb < 4; ++jb) acc1[ib][jb] = acc0[ib][jb];
+      if constexpr (STREAM) {
+        // the run's first unit peeled off the loop: its substeps wait for their
+        // own A fragments (a loop would wait for all of them at its head)
+        step(std::integral_constant<int, XPEEL>{}, j, acc0, acc1);  // -> acc0
         ++j;
+        for (; j + 1 < jend; j += 2) {
+          step(in_run, j, acc1, acc0);
+          step(in_run, j + 1, acc0, acc1);
+        }
+        if (j < jend) {
+          step(in_run, j, acc1, acc0);  // -> acc1
+          ++j;
+        } else {
+#pragma unroll
+          for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+            for (int jb = 0; jb < 4; ++jb) acc1[ib][jb] = acc0[ib][jb];
+        }
+      } else {
+        for (; j + 1 < jend; j += 2) {
+          step(in_run, j, acc0, acc1);
+          step(in_run, j + 1, acc1, acc0);
+        }
+        if (j < jend) {
+          step(in_run, j, acc0, acc1);
+#pragma unroll
+          for (int ib = 0; ib < 2; ++ib)
+#pragma unroll
+            for (int jb = 0; jb < 4; ++jb) acc1[ib][jb] = acc0[ib][jb];
+          ++j;
+        }
       }
     }
     epi_all(acc1);  // the last unit's epilogue
+#ifdef PX_TRACE
+    pwait_vm0();
+    PTRACE(90, 0)  // (kernel end, stores drained)
+#endif
   };
   if (wave < 4) run(std::integral_constant<int, 0>{});
   else run(std::integral_constant<int, PEPI_OFF1>{});

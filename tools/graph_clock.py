@@ -1,7 +1,8 @@
 """In-graph clock and unit timing of the panel GEMM (a PX_TRACE build of the
 library): replays the bench's ViT-S 518^2 B=48 forward graph back to back, as
 bench.py times it, then reads the s_memtime / s_memrealtime stamps the LAST
-panel launch of the last forward (block 11's fc1) left for workgroups 0-7.
+panel launch of the last forward (block 11's fc1) left for the traced
+workgroups (gemm_panel.hip PTRACE).
 
     python tools/graph_clock.py LIB [--steps 40] [--batch 48]
 
@@ -74,7 +75,7 @@ def main():
           f"in-kernel clock {np.median(ck):.3f} GHz, unit {np.median(ul):.0f} ticks = "
           f"{np.median(ul) / np.median(ck) / 1e3:.2f} us")
     if (t[:, :, 95, 3] > 0).all():
-        print(f"entry -> end {np.median(rt[:, :, 90] - rt[:, :, 95]):.1f} us (workgroups 0-7)")
+        print(f"entry -> end {np.median(rt[:, :, 90] - rt[:, :, 95]):.1f} us (traced workgroups)")
     ctx.destroy()
     eng.destroy()
 
