@@ -122,6 +122,16 @@ const char* mde_last_error(void);
  * value out of range. */
 int mde_tuning_set(const char* name, int value);
 int mde_tuning_get(const char* name, int* value);
+/* For tests and tools: the route the calling thread's last GEMM-family launch
+ * (every mde_op_linear*, qkv*, conv3x3*, conv_transpose*, patch_embed and
+ * depth_head* op, and each such layer of an enqueue) took, as one line of
+ * key=value fields, e.g. "kind=tile bm=128 bn=128 wm=2 wn=2 bk=32 stages=3
+ * slices=1 fused=0 resize_first=0".  kind: none (nothing launched yet, or an
+ * empty problem), tile, split_store, split_resid (these three with every
+ * field: block tile, wave grid, K-step, LDS ring depth, split-K slices, fused
+ * split tail, a resize launch in front), conv_direct (resize_first only),
+ * panel, gemm256.  MDE_ERR_ARG: null buffer, or n too small (128 suffices). */
+int mde_debug_last_gemm_route(char* buf, size_t n);
 
 /* ---- engine (replaces get_engine / ICudaEngine) ----------------------- */
 int mde_engine_load(const char* packed_path, int device, mde_engine** out);

@@ -61,6 +61,7 @@ PROTOTYPES = {
     "mde_last_error": [],
     "mde_tuning_set": [c_char_p, c_int],
     "mde_tuning_get": [c_char_p, P(c_int)],
+    "mde_debug_last_gemm_route": [c_char_p, c_size_t],
     "mde_engine_load": [c_char_p, c_int, P(c_void_p)],
     "mde_engine_load_memory": [c_void_p, c_size_t, c_int, P(c_void_p)],
     "mde_engine_destroy": [c_void_p],
@@ -304,6 +305,15 @@ def tuning(**switches):
     finally:
         for k, v in old.items():
             set_tuning(k, v)
+
+
+def last_gemm_route() -> dict:
+    """The route this thread's last GEMM-family launch took (include/mde.h
+    mde_debug_last_gemm_route): {"kind": "tile", "bm": 128, ...}."""
+    buf = C.create_string_buffer(256)
+    call("mde_debug_last_gemm_route", buf, len(buf))
+    fields = dict(f.split("=", 1) for f in buf.value.decode().split())
+    return {k: v if k == "kind" else int(v) for k, v in fields.items()}
 
 
 def exported_symbols():

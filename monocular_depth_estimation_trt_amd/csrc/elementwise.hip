@@ -520,7 +520,7 @@ hipError_t launch_splitk_resid(const float* P, int S, int M, int N, const float*
 }
 
 namespace {
-// second half of the E_STORE split-K path (gemm.hip launch_split_store): one
+// second half of the E_STORE split-K path (gemm.hip launch_split): one
 // thread per 8 columns of a row, slices added in order 0..S-1, then the
 // E_STORE epilogue of tile_epilogue.h (bias, activation, then the residual
 // adds, one rounding to f16)

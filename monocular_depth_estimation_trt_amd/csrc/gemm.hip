@@ -31,7 +31,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 
+#include "gemm_route.h"
 #include "mde_device.h"
 #include "mde_ops.h"
 #include "tile_epilogue.h"
@@ -573,14 +575,42 @@ __global__ void __launch_bounds__(WM * WN * 64) MDE_GEMM_WPE_ATTR
   if (!staged) store_tile<EM, TM, TN>(p, acc, mrow, n0 + wn * TN * 16 + (lane >> 4) * 4, lane, slice);
 }
 
-template <int BM, int BN, int WM, int WN, int AM, int EM, int BKSEL = MDE_GEMM_BK, int STG = 0>
-hipError_t run(const GemmParams& p, hipStream_t st) {
-  const int gm = (p.M + BM - 1) / BM, gn = (p.N + BN - 1) / BN;
-  const long long blocks = (long long)gm * gn;
-  if (blocks <= 0) return hipSuccess;
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, BKSEL, WM, WN, AM, EM, STG>), dim3((unsigned)blocks), dim3(WM * WN * 64), 0,
-                     st, p);
-  return hipGetLastError();
+// ---- host side: the route (gemm_route.h), then one launcher -------------------
+
+// The tile configurations gemm_kernel is instantiated with and, per A mode,
+// the epilogues each is built for (bit e: EMode e; fsplit: the fused split-K
+// form) -- exactly the kernels the routes below ask for (DESIGN.md section
+// 4b).  stg: the kernel's STG argument (0: the ring depth of its BK).
+struct TileCfg {
+  int bm, bn, wm, wn, bk, stg, modes[3], fsplit[2];
+};
+enum : int { mS = 1 << E_STORE, mQ = 1 << E_QKV, mR = 1 << E_RESID, mP = 1 << E_PATCH, mC = 1 << E_CONVT,
+             mH = 1 << E_HEAD, mX = 1 << E_PARTIAL, mAll = mS | mQ | mR | mP | mC };
+enum Tile : int { T128x32, T128x64, T64, T64_DEEP, T32x64_DEEP, T128, T128_BK32, T128_W8, T256x128_BK32, T_COUNT };
+constexpr TileCfg kTiles[T_COUNT] = {
+    //                                 A_DENSE       A_CONV3   A_CONV3_UP   fused: dense, im2col
+    {128, 32, 4, 1, MDE_GEMM_BK, 0, {mS, mS, mS | mH}, {0, 0}},                 // T128x32
+    {128, 64, 4, 1, MDE_GEMM_BK, 0, {mS | mR, mS, mS}, {0, 0}},                 // T128x64
+    {64, 64, 2, 2, MDE_GEMM_BK, 0, {mAll | mX, mS | mX, mS}, {mS | mR, mS}},    // T64
+    {64, 64, 2, 2, MDE_GEMM_BK, 4, {mAll | mX, mX, 0}, {mS | mR, mS}},          // T64_DEEP
+    {32, 64, 2, 2, 64, 4, {mR, 0, 0}, {0, 0}},                                  // T32x64_DEEP
+    {128, 128, 2, 2, MDE_GEMM_BK, 0, {mAll | mX, mS, mS}, {mR, 0}},             // T128
+    {128, 128, 2, 2, 32, 0, {mS | mQ | mP | mC, 0, 0}, {0, 0}},                 // T128_BK32
+    {128, 128, 2, 4, MDE_GEMM_BK, 0, {mS | mQ | mX, 0, 0}, {mR, 0}},            // T128_W8
+    {256, 128, 4, 2, 32, 0, {mR, 0, 0}, {0, 0}},                                // T256x128_BK32
+};
+constexpr int ring_stages(const TileCfg& c) { return c.stg ? c.stg : (c.bk == 32 ? MDE_BK32_STAGES : MDE_GEMM_STAGES); }
+constexpr bool tile_has(int t, int am, int em, bool split) {
+  if (t < 0 || t >= T_COUNT || am < 0 || am > (split ? A_CONV3 : A_CONV3_UP) || em < 0 || em > E_PARTIAL) return false;
+  return ((split ? kTiles[t].fsplit[am] : kTiles[t].modes[am]) >> em) & 1;
+}
+
+long long tiles(int M, int N, int bm, int bn) { return (long long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); }
+
+// S slices of nk K-steps, rounded so that every slice is non-empty
+int even_slices(int nk, int S) {
+  const int per = (nk + S - 1) / S;
+  return (nk + per - 1) / per;
 }
 
 // dense short-K stores (K <= 768) take the BK 32 / 3-stage / three-per-CU
@@ -610,68 +640,52 @@ bool w8small(long long wgs) { return knob(KNOB_W8SMALL) && wgs < 512; }
 // "narrow_resid".
 bool narrow_resid(const GemmParams& p) {
   if (!knob(KNOB_NARROW_RESID) || p.amode != A_DENSE || p.emode != E_RESID) return false;
-  const long long t64 = (long long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-  const long long t32 = (long long)((p.M + 31) / 32) * ((p.N + 63) / 64);
-  return t64 < 256 && t32 >= 192 && t32 <= 512;
+  const long long t32 = tiles(p.M, p.N, 32, 64);
+  return tiles(p.M, p.N, 64, 64) < 256 && t32 >= 192 && t32 <= 512;
 }
 
-template <int AM, int EM>
-hipError_t dispatch(const GemmParams& p, hipStream_t st) {
-  if constexpr (EM == E_HEAD) {
-    return run<128, 32, 4, 1, AM, EM>(p, st);
-  } else {
-    if constexpr (EM == E_STORE) {
-      if (p.N <= 32) return run<128, 32, 4, 1, AM, EM>(p, st);
-      if (p.N <= 64) {
-        if (p.M >= 128 * 256) return run<128, 64, 4, 1, AM, EM>(p, st);
-        return run<64, 64, 2, 2, AM, EM>(p, st);
-      }
-    }
-    const long long big = (long long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    if constexpr (AM == A_DENSE && EM == E_RESID) {
-      // residual updates with at least two rounds of 256 x 128 tiles (8 waves,
-      // BK 32 x 3 stages, two workgroups per CU): 25 % fewer L2 -> LDS bytes per
-      // FLOP and twice the rows per workgroup for the read-modify-write
-      // epilogue.  ViT-S B = 48, same box, two passes: proj 0.685 / 0.690 ->
-      // 0.611 / 0.606 ms, fc2 1.493 / 1.503 -> 1.401 / 1.394 ms per forward,
-      // qkv / fc1 unchanged on this tile (profiles/r03_v3_*)
-      const long long t256 = (long long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-      if (t256 >= 512) return run<256, 128, 4, 2, AM, EM, 32>(p, st);
-      // short-K residual updates (ViT-S proj, K 384) on 128 x 64 tiles: 48 KB
-      // LDS with full fp32 staging, three workgroups per CU (B=28: proj
-      // 0.427/0.431 -> 0.419/0.425 ms per forward, two same-box runs; fc2 at
-      // K 1536 loses, 0.86 -> 0.97)
-      if (p.K <= 384 && big >= kBigTileMin) return run<128, 64, 4, 1, AM, EM>(p, st);
-      if (narrow_resid(p)) return run<32, 64, 2, 2, AM, EM, 64, 4>(p, st);
-    }
-    if (big >= kBigTileMin) {
-      // short-K stores (ViT-S/B qkv, fc1: K 384 / 768 -> 6-12 K-steps, the
-      // epilogue a third of the launch) gain from the third workgroup per CU
-      // (B=28 ViT-S: fc1 1.30 -> 1.10 ms, qkv 0.97 -> 0.89 per forward); the
-      // residual updates and K >= 1024 do not (fc2 0.85 -> 0.96 with two fp32
-      // staging passes, proj 0.43 -> 0.45 even with f16 staging of the
-      // update; ViT-L B=8 qkv 2.56 -> 2.67)
-      if constexpr (AM == A_DENSE && (EM == E_STORE || EM == E_QKV)) {
-        if (p.K <= kBk32Kmax) return run<128, 128, 2, 2, AM, EM, 32>(p, st);
-        if (w8small(big)) return run<128, 128, 2, 4, AM, EM>(p, st);
-      }
-      // the patch embed (K 672) and the resize-layer ConvTs (K 48 / 96) too:
-      // ViT-S B = 48, per layer, two same-box runs: patch_embed 86.4 / 85.8 ->
-      // 83.5 / 83.8 us, convT4 57.8 / 59.1 -> 48.6 / 50.6, convT2 34.7 / 34.8
-      // -> 31.4 / 32.4 (profiles/r05_patch_convt_bk32.txt)
-      if constexpr (AM == A_DENSE && (EM == E_PATCH || EM == E_CONVT)) {
-        if (p.K <= kBk32Kmax) return run<128, 128, 2, 2, AM, EM, 32>(p, st);
-      }
-      return run<128, 128, 2, 2, AM, EM>(p, st);
-    }
-    if constexpr (AM == A_DENSE) {
-      const long long t64 = (long long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-      if (deep64(t64)) return run<64, 64, 2, 2, AM, EM, 64, 4>(p, st);
-      // (a 3-deep ring for grids of 512-768 tiles measured no gain: ViT-S B=1
-      // fc1, 528 tiles, 0.134 -> 0.136 ms per forward, profiles/r03_v11_*)
-    }
-    return run<64, 64, 2, 2, AM, EM>(p, st);
+// the tile of an unsplit gemm_kernel launch (p's modes are a valid pair)
+Tile pick_tile(const GemmParams& p) {
+  const int em = p.emode;
+  const bool dense = p.amode == A_DENSE;
+  if (em == E_HEAD) return T128x32;
+  if (em == E_STORE) {
+    if (p.N <= 32) return T128x32;
+    if (p.N <= 64) return p.M >= 128 * 256 ? T128x64 : T64;
   }
+  const long long big = tiles(p.M, p.N, 128, 128);
+  if (dense && em == E_RESID) {
+    // residual updates with at least two rounds of 256 x 128 tiles (8 waves,
+    // BK 32 x 3 stages, two workgroups per CU): 25 % fewer L2 -> LDS bytes per
+    // FLOP and twice the rows per workgroup for the read-modify-write
+    // epilogue.  ViT-S B = 48, same box, two passes: proj 0.685 / 0.690 ->
+    // 0.611 / 0.606 ms, fc2 1.493 / 1.503 -> 1.401 / 1.394 ms per forward,
+    // qkv / fc1 unchanged on this tile (profiles/r03_v3_*)
+    if (tiles(p.M, p.N, 256, 128) >= 512) return T256x128_BK32;
+    // short-K residual updates (ViT-S proj, K 384) on 128 x 64 tiles: 48 KB
+    // LDS with full fp32 staging, three workgroups per CU (B=28: proj
+    // 0.427/0.431 -> 0.419/0.425 ms per forward, two same-box runs; fc2 at
+    // K 1536 loses, 0.86 -> 0.97)
+    if (p.K <= 384 && big >= kBigTileMin) return T128x64;
+    if (narrow_resid(p)) return T32x64_DEEP;
+  }
+  if (big >= kBigTileMin) {
+    // short-K stores (ViT-S/B qkv, fc1: K 384 / 768 -> 6-12 K-steps, the
+    // epilogue a third of the launch) gain from the third workgroup per CU
+    // (B=28 ViT-S: fc1 1.30 -> 1.10 ms, qkv 0.97 -> 0.89 per forward); the
+    // residual updates and K >= 1024 do not (fc2 0.85 -> 0.96 with two fp32
+    // staging passes, proj 0.43 -> 0.45 even with f16 staging of the
+    // update; ViT-L B=8 qkv 2.56 -> 2.67)
+    // the patch embed (K 672) and the resize-layer ConvTs (K 48 / 96) too:
+    // ViT-S B = 48, per layer, two same-box runs: patch_embed 86.4 / 85.8 ->
+    // 83.5 / 83.8 us, convT4 57.8 / 59.1 -> 48.6 / 50.6, convT2 34.7 / 34.8
+    // -> 31.4 / 32.4 (profiles/r05_patch_convt_bk32.txt)
+    if (dense && em != E_RESID && p.K <= kBk32Kmax) return T128_BK32;
+    return dense && (em == E_STORE || em == E_QKV) && w8small(big) ? T128_W8 : T128;
+  }
+  // (a 3-deep ring for grids of 512-768 tiles measured no gain: ViT-S B=1
+  // fc1, 528 tiles, 0.134 -> 0.136 ms per forward, profiles/r03_v11_*)
+  return dense && deep64(tiles(p.M, p.N, 64, 64)) ? T64_DEEP : T64;
 }
 
 // Direct-conv tiles are 8 x 16 output pixels per image: on small maps most of
@@ -687,6 +701,19 @@ bool prefer_im2col(const GemmParams& p) {
   return p.cc >= 256 && (double)p.oh * p.ow < 0.6 * tiles;
 }
 
+// The E_STORE split-K policy's ESTIMATE of the unsplit launch's workgroups,
+// not what the route would launch: 128^2 or 64^2 tiles only (no N <= 64
+// tiles, no panel or 256^2 kernel), one direct-conv tiling for every conv
+// kernel.  The slice counts were measured with it.
+long long unsplit_wgs_estimate(const GemmParams& p) {
+  if (p.amode == A_CONV3 && conv_direct_supported(p) && !prefer_im2col(p)) {
+    const int bn = p.N <= 32 ? 32 : (p.N <= 64 ? 64 : 128);
+    return (long long)p.cb * ((p.oh + 7) / 8) * ((p.ow + 15) / 16) * ((p.N + bn - 1) / bn);
+  }
+  const long long big = tiles(p.M, p.N, 128, 128);
+  return big >= kBigTileMin ? big : tiles(p.M, p.N, 64, 64);
+}
+
 // E_STORE split-K: slices of the K loop on 64^2 tiles into the fp32
 // workspace, then launch_splitk_store sums them in slice order and runs the
 // epilogue (deterministic).  For grids that leave most of the chip idle: the
@@ -699,16 +726,8 @@ int store_split_slices(const GemmParams& p) {
   if (p.amode == A_CONV3 && p.stride != 1 && p.stride != 2) return 1;
   if (!knob(KNOB_SPLITK)) return 1;
   const int nk = (p.K + 63) / 64;
-  const long long t64 = (long long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-  // workgroups of the unsplit launch
-  long long wgs;
-  if (p.amode == A_CONV3 && conv_direct_supported(p) && !prefer_im2col(p)) {
-    const int bn = p.N <= 32 ? 32 : (p.N <= 64 ? 64 : 128);
-    wgs = (long long)p.cb * ((p.oh + 7) / 8) * ((p.ow + 15) / 16) * ((p.N + bn - 1) / bn);
-  } else {
-    const long long big = (long long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    wgs = big >= kBigTileMin ? big : t64;
-  }
+  const long long t64 = tiles(p.M, p.N, 64, 64);
+  const long long wgs = unsplit_wgs_estimate(p);
   // at least 12 K-steps: the 64-channel convs of the ViT-S DPT (K 576, 9
   // steps) run better unsplit (ViT-S B=1 0.925 -> 0.902 ms per forward with
   // 12 vs 8; 16: 0.909)
@@ -729,9 +748,7 @@ int store_split_slices(const GemmParams& p) {
   S = S < nk / 4 ? S : nk / 4;  // >= 4 K-steps per slice
   S = S < 16 ? S : 16;
   while (S > 1 && (size_t)S * p.M * p.N > p.partial_cap) --S;
-  if (S <= 1) return 1;
-  const int per = (nk + S - 1) / S;
-  return (nk + per - 1) / per;  // every slice non-empty
+  return S <= 1 ? 1 : even_slices(nk, S);
 }
 
 // the fused split-K form (GemmParams::tile_cnt) applies: switch on, counters
@@ -741,34 +758,7 @@ bool fused_split(const GemmParams& p, long long tiles, int S, int BM, int BN) {
          (size_t)S * (size_t)tiles * (size_t)BM * BN <= p.slot_cap && ((uintptr_t)p.partial & 15) == 0;
 }
 
-template <int AM>
-hipError_t launch_split_store(const GemmParams& p, int S, hipStream_t st) {
-  const unsigned tiles = (unsigned)(((p.M + 63) / 64) * ((p.N + 63) / 64));
-  if (fused_split(p, tiles, S, 64, 64)) {
-    if (deep64((long long)tiles * S))
-      hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, AM, E_STORE, 4, true>), dim3(tiles, (unsigned)S),
-                         dim3(256), 0, st, p);
-    else
-      hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, AM, E_STORE, 0, true>), dim3(tiles, (unsigned)S),
-                         dim3(256), 0, st, p);
-    return hipGetLastError();
-  }
-  GemmParams q = p;
-  q.emode = E_PARTIAL;
-  q.x32 = p.partial;
-  q.ldo = p.N;
-  if (deep64((long long)tiles * S))
-    hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, AM, E_PARTIAL, 4>), dim3(tiles, (unsigned)S), dim3(256),
-                       0, st, q);
-  else
-    hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, AM, E_PARTIAL>), dim3(tiles, (unsigned)S), dim3(256), 0,
-                       st, q);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return launch_splitk_store(p.partial, S, p, st);
-}
-
-// folded-LayerNorm operands consistent with the problem (launch_gemm)
+// folded-LayerNorm operands consistent with the problem (gemm_route)
 bool lnst_valid(const GemmParams& p) {
   if (p.lnst_out && !MDE_EPI_LDS) return false;
   return !((p.lnst_ns * 32 != (p.lnst_out ? p.N : p.K)) ||
@@ -779,27 +769,57 @@ bool lnst_valid(const GemmParams& p) {
            (p.lnst_in && (!p.lnc1 || p.amode != A_DENSE)) || (p.lnst_out && !p.xh));
 }
 
+// a gemm_kernel route: `slices` K slices on tile t
+GemmRoute tile_route(int kind, Tile t, int slices, bool fused) {
+  const TileCfg& c = kTiles[t];
+  return {kind, c.bm, c.bn, c.wm, c.wn, c.bk, ring_stages(c), slices, fused, 0};
+}
+
+// E_RESID split-K, small M and long K (B = 1 fc2: 132 64^2 tiles x 24
+// K-steps): S slices of the K loop fill the chip, a second kernel adds them
+// in slice order.  When 128^2 tiles x 4 slices still give >= 320 workgroups
+// (ViT-L / VGGT B = 1: 88 tiles), the 128^2 tiles halve the L2 -> LDS bytes
+// per FLOP of the 64^2 ones; `partial` holds 4 slices (engine contract).
+GemmRoute split_resid_route(const GemmParams& p) {
+  const int nk = (p.K + 63) / 64;
+  const long long t128 = tiles(p.M, p.N, 128, 128), t64 = tiles(p.M, p.N, 64, 64);
+  const bool big = t128 * 4 >= 320 && nk >= 16;
+  int S = big ? 4 : (p.splitk < nk ? p.splitk : nk);
+  // keep the 64^2 slices within two workgroups per CU (deep ring; same slices with "deep64" off)
+  while (!big && S > 2 && t64 * S > 512) --S;
+  S = even_slices(nk, S);
+  const Tile t = big ? (w8small(t128 * S) ? T128_W8 : T128) : (deep64(t64 * S) ? T64_DEEP : T64);
+  // fused: one launch, the slices' tails add the slots and run the E_RESID
+  // epilogue (LN partials included) on the tile's last slice
+  return tile_route(ROUTE_SPLIT_RESID, t, S, fused_split(p, big ? t128 : t64, S, kTiles[t].bm, kTiles[t].bn));
+}
+
+thread_local GemmRoute t_last_route;
+
 }  // namespace
 
-int gemm_store_split_slices(const GemmParams& p) { return store_split_slices(p); }
-
-hipError_t launch_gemm(const GemmParams& p, hipStream_t st) {
-  if (p.M <= 0 || p.N <= 0) return hipSuccess;
+// The checks run in the order launch_gemm has always made them, so a route
+// that leaves early skips the later ones:
+//  * a res1_up problem the direct conv takes is checked by launch_conv3 alone
+//    (none of the K / ldw / lda / ldo checks here);
+//  * the E_STORE split and the direct conv leave before xh's 16-byte check;
+//  * the E_RESID split leaves before lnst_valid: its lnst_out goes to the
+//    reduce launch (or the fused tail) unchecked here;
+//  * the direct conv leaves before the (amode, emode) pair is checked.
+hipError_t gemm_route(const GemmParams& p, GemmRoute& r) {
+  const auto take = [&r](const GemmRoute& x) { r = x; return hipSuccess; };
+  if (p.M <= 0 || p.N <= 0) return take({ROUTE_NONE});
   if (p.res1_up) {
     // res1 = upsample(res1_up): read through it by the direct conv's
     // epilogue, or written into res1 first for every other route
     if (!p.res1 || p.amode != A_CONV3 || p.emode != E_STORE || p.res1_uh <= 0 || p.res1_uw <= 0 || (p.N & 7))
       return hipErrorInvalidValue;
+    if (store_split_slices(p) <= 1 && !prefer_im2col(p) && conv3_takes_res1_up(p)) return take({ROUTE_CONV_DIRECT});
     GemmParams q = p;
-    if (store_split_slices(p) <= 1 && !prefer_im2col(p) && conv3_takes_res1_up(p)) {
-      q.res1 = nullptr;
-      return launch_conv3(q, st);
-    }
-    const hipError_t e = launch_resize(p.res1_up, const_cast<h16*>(p.res1), p.cb, p.res1_uh, p.res1_uw, p.N, p.oh,
-                                       p.ow, st);
-    if (e != hipSuccess) return e;
     q.res1_up = nullptr;
-    return launch_gemm(q, st);
+    const hipError_t e = gemm_route(q, r);
+    r.resize_first = 1;
+    return e;
   }
   if (p.K <= 0 || (p.K & 7) || (p.N & 7) || (p.ldw & 63) || p.ldw < ((p.K + 63) / 64) * 64)
     return hipErrorInvalidValue;
@@ -816,100 +836,100 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t st) {
   if (p.emode == E_HEAD && (p.N != 32 || p.amode == A_DENSE)) return hipErrorInvalidValue;
   if (const int S = store_split_slices(p); S > 1) {
     if ((p.ldo & 7) || ((uintptr_t)p.partial & 15)) return hipErrorInvalidValue;
-    return p.amode == A_DENSE ? launch_split_store<A_DENSE>(p, S, st) : launch_split_store<A_CONV3>(p, S, st);
+    const long long t64 = tiles(p.M, p.N, 64, 64);
+    return take(tile_route(ROUTE_SPLIT_STORE, deep64(t64 * S) ? T64_DEEP : T64, S, fused_split(p, t64, S, 64, 64)));
   }
-  if (p.amode != A_DENSE && conv_direct_supported(p) && !prefer_im2col(p))
-    return launch_conv3(p, st);
+  if (p.amode != A_DENSE && conv_direct_supported(p) && !prefer_im2col(p)) return take({ROUTE_CONV_DIRECT});
   if ((p.emode == E_RESID || p.emode == E_PATCH) && p.xh && ((uintptr_t)p.xh & 15)) return hipErrorInvalidValue;
-  if (p.emode == E_RESID && p.splitk > 1 && p.partial && p.amode == A_DENSE && !narrow_resid(p)) {
-    // small M, long K (B = 1 fc2: 132 64^2 tiles x 24 K-steps): S slices of
-    // the K loop fill the chip, a second kernel adds them in slice order.
-    // When 128^2 tiles x 4 slices still give >= 320 workgroups (ViT-L /
-    // VGGT B = 1: 88 tiles), the 128^2 tiles halve the L2 -> LDS bytes per
-    // FLOP of the 64^2 ones; `partial` holds 4 slices (engine contract)
-    const int nk = (p.K + 63) / 64;
-    const long long t128 = (long long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    const bool big = t128 * 4 >= 320 && nk >= 16;
-    int S = big ? 4 : (p.splitk < nk ? p.splitk : nk);
-    if (!big) {  // keep the 64^2 slices within two workgroups per CU (deep ring; same slices with "deep64" off)
-      const long long t64 = (long long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-      while (S > 2 && t64 * S > 512) --S;
-    }
-    const int per = (nk + S - 1) / S;
-    S = (nk + per - 1) / per;  // every slice non-empty
-    const long long t64 = (long long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-    if (fused_split(p, big ? t128 : t64, S, big ? 128 : 64, big ? 128 : 64)) {
-      // one launch: the slices' tails add the slots and run the E_RESID
-      // epilogue (LN partials included) on the tile's last slice
-      if (big && w8small(t128 * S)) {
-        hipLaunchKernelGGL((gemm_kernel<128, 128, MDE_GEMM_BK, 2, 4, A_DENSE, E_RESID, 0, true>),
-                           dim3((unsigned)t128, (unsigned)S), dim3(512), 0, st, p);
-      } else if (big) {
-        hipLaunchKernelGGL((gemm_kernel<128, 128, MDE_GEMM_BK, 2, 2, A_DENSE, E_RESID, 0, true>),
-                           dim3((unsigned)t128, (unsigned)S), dim3(256), 0, st, p);
-      } else if (deep64(t64 * S)) {
-        hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, A_DENSE, E_RESID, 4, true>), dim3((unsigned)t64, (unsigned)S),
-                           dim3(256), 0, st, p);
-      } else {
-        hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, A_DENSE, E_RESID, 0, true>), dim3((unsigned)t64, (unsigned)S),
-                           dim3(256), 0, st, p);
-      }
-      return hipGetLastError();
-    }
-    GemmParams q = p;
-    q.emode = E_PARTIAL;
-    q.x32 = p.partial;
-    q.ldo = p.N;
-    q.bias = nullptr;
-    q.ls = nullptr;
-    q.lnst_out = nullptr;  // the reduce kernel writes the LN partials
-    if (big && w8small(t128 * S)) {
-      hipLaunchKernelGGL((gemm_kernel<128, 128, MDE_GEMM_BK, 2, 4, A_DENSE, E_PARTIAL>), dim3((unsigned)t128, (unsigned)S),
-                         dim3(512), 0, st, q);
-    } else if (big) {
-      hipLaunchKernelGGL((gemm_kernel<128, 128, MDE_GEMM_BK, 2, 2, A_DENSE, E_PARTIAL>), dim3((unsigned)t128, (unsigned)S),
-                         dim3(256), 0, st, q);
-    } else {
-      const unsigned tiles = (unsigned)(((p.M + 63) / 64) * ((p.N + 63) / 64));
-      if (deep64((long long)tiles * S))
-        hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, A_DENSE, E_PARTIAL, 4>), dim3(tiles, (unsigned)S),
-                           dim3(256), 0, st, q);
-      else
-        hipLaunchKernelGGL((gemm_kernel<64, 64, MDE_GEMM_BK, 2, 2, A_DENSE, E_PARTIAL>), dim3(tiles, (unsigned)S),
-                           dim3(256), 0, st, q);
-    }
-    const hipError_t e = hipGetLastError();
+  if (p.emode == E_RESID && p.splitk > 1 && p.partial && p.amode == A_DENSE && !narrow_resid(p))
+    return take(split_resid_route(p));
+  // folded LayerNorm: the panel kernel or the 128^2 / 64^2 kernels of this
+  // file (partials per 32-column slice from the LDS-staged epilogue, the fold
+  // after the main loop; a tile that falls back to the direct epilogue writes
+  // NaN partials), never the 256^2 kernel
+  const bool lnfold = p.lnst_out || p.lnst_in;
+  if (lnfold && !lnst_valid(p)) return hipErrorInvalidValue;
+  if (panel_gemm_eligible(p)) return take({ROUTE_PANEL});
+  if (!lnfold && gemm256_eligible(p)) return take({ROUTE_GEMM256});
+  const Tile t = pick_tile(p);  // (E_PARTIAL is the split routes' own: not a caller's mode)
+  if (p.emode == E_PARTIAL || !tile_has(t, p.amode, p.emode, false)) return hipErrorInvalidValue;
+  return take(tile_route(ROUTE_TILE, t, 1, false));
+}
+
+const GemmRoute& gemm_last_route() { return t_last_route; }
+
+namespace {
+
+// f(std::integral_constant<int, x>) for x in [0, N); any other x is an invalid argument
+template <int N, class F>
+hipError_t with_constant(int x, F&& f) {
+  if constexpr (N == 0) return hipErrorInvalidValue;
+  else return x == N - 1 ? f(std::integral_constant<int, N - 1>{}) : with_constant<N - 1>(x, f);
+}
+
+// gemm_kernel on r's row of the table with p's modes (fused: its fused split-K form), over r's tiles x slices
+hipError_t launch_tiles(const GemmRoute& r, const GemmParams& p, bool fused, hipStream_t st) {
+  int t = 0;
+  for (const TileCfg& c : kTiles) {
+    if (c.bm == r.bm && c.bn == r.bn && c.wm == r.wm && c.wn == r.wn && c.bk == r.bk && ring_stages(c) == r.stages) break;
+    ++t;
+  }
+  const dim3 grid((unsigned)tiles(p.M, p.N, r.bm, r.bn), (unsigned)r.slices);
+  return with_constant<T_COUNT>(t, [&](auto T) {
+    return with_constant<A_CONV3_UP + 1>(p.amode, [&](auto AM) {
+      return with_constant<E_PARTIAL + 1>(p.emode, [&](auto EM) {
+        return with_constant<2>(fused, [&](auto FUSED) {
+          constexpr int am = decltype(AM)::value, em = decltype(EM)::value, fs = decltype(FUSED)::value;
+          if constexpr (tile_has(decltype(T)::value, am, em, fs)) {
+            constexpr TileCfg c = kTiles[decltype(T)::value];
+            hipLaunchKernelGGL((gemm_kernel<c.bm, c.bn, c.bk, c.wm, c.wn, am, em, c.stg, fs != 0>), grid,
+                               dim3(c.wm * c.wn * 64), 0, st, p);
+            return hipGetLastError();
+          } else {
+            return hipErrorInvalidValue;
+          }
+        });
+      });
+    });
+  });
+}
+
+// the split-K routes: the fused form in one launch, or the slices as E_PARTIAL tiles into the workspace and
+// then the reduce launch, which adds them in slice order and runs p's epilogue (bias, LayerScale, LN partials)
+hipError_t launch_split(const GemmRoute& r, const GemmParams& p, hipStream_t st) {
+  if (r.fused) return launch_tiles(r, p, true, st);
+  GemmParams q = p;
+  q.emode = E_PARTIAL, q.x32 = p.partial, q.ldo = p.N;
+  q.bias = q.ls = nullptr, q.lnst_out = nullptr;
+  const hipError_t e = launch_tiles(r, q, false, st);
+  if (e != hipSuccess) return e;
+  if (r.kind == ROUTE_SPLIT_STORE) return launch_splitk_store(p.partial, r.slices, p, st);
+  return launch_splitk_resid(p.partial, r.slices, p.M, p.N, p.bias, p.ls, p.x32, p.xh, p.ldo, st, p.lnst_out);
+}
+
+}  // namespace
+
+hipError_t launch_gemm(const GemmParams& p, hipStream_t st) {
+  GemmRoute r;
+  hipError_t e = gemm_route(p, r);
+  if (e != hipSuccess) return e;
+  t_last_route = r;
+  GemmParams q = p;
+  if (r.resize_first) {
+    e = launch_resize(p.res1_up, const_cast<h16*>(p.res1), p.cb, p.res1_uh, p.res1_uw, p.N, p.oh, p.ow, st);
     if (e != hipSuccess) return e;
-    return launch_splitk_resid(p.partial, S, p.M, p.N, p.bias, p.ls, p.x32, p.xh, p.ldo, st, p.lnst_out);
+    q.res1_up = nullptr;
   }
-  if (p.lnst_out || p.lnst_in) {
-    // folded LayerNorm: the 128^2 / 64^2 kernels of this file (partials per
-    // 32-column slice from the LDS-staged epilogue, the fold after the main loop;
-    // a tile that falls back to the direct epilogue writes NaN partials)
-    if (!lnst_valid(p)) return hipErrorInvalidValue;
-    if (panel_gemm_eligible(p)) return launch_panel_gemm(p, st);
-  } else if (panel_gemm_eligible(p)) {
-    return launch_panel_gemm(p, st);
-  } else if (gemm256_eligible(p)) {
-    return launch_gemm256(p, st);
-  }
-  switch (p.amode) {
-    case A_DENSE:
-      switch (p.emode) {
-        case E_STORE: return dispatch<A_DENSE, E_STORE>(p, st);
-        case E_QKV: return dispatch<A_DENSE, E_QKV>(p, st);
-        case E_RESID: return dispatch<A_DENSE, E_RESID>(p, st);
-        case E_PATCH: return dispatch<A_DENSE, E_PATCH>(p, st);
-        case E_CONVT: return dispatch<A_DENSE, E_CONVT>(p, st);
-        default: return hipErrorInvalidValue;
-      }
-    case A_CONV3:
-      if (p.emode == E_STORE) return dispatch<A_CONV3, E_STORE>(p, st);
-      return hipErrorInvalidValue;
-    case A_CONV3_UP:
-      if (p.emode == E_STORE) return dispatch<A_CONV3_UP, E_STORE>(p, st);
-      if (p.emode == E_HEAD) return dispatch<A_CONV3_UP, E_HEAD>(p, st);
-      return hipErrorInvalidValue;
+  switch (r.kind) {
+    case ROUTE_NONE: return hipSuccess;
+    case ROUTE_TILE: return launch_tiles(r, q, false, st);
+    case ROUTE_SPLIT_STORE:
+    case ROUTE_SPLIT_RESID: return launch_split(r, q, st);
+    case ROUTE_CONV_DIRECT:
+      if (q.res1_up) q.res1 = nullptr;  // the conv's epilogue reads res1 through res1_up
+      return launch_conv3(q, st);
+    case ROUTE_PANEL: return launch_panel_gemm(q, st);
+    case ROUTE_GEMM256: return launch_gemm256(q, st);
     default: return hipErrorInvalidValue;
   }
 }

@@ -1107,40 +1107,35 @@ bool panel_gemm_eligible(const GemmParams& p) {
   return false;
 }
 
+// p's (emode, act, LayerNorm folded on its input) as the kernels' template
+// arguments -- f(EM, ACT, FOLD) on integral constants -- for the variants
+// panel_gemm_eligible admits: no activation on E_QKV / E_RESID, no fold on E_RESID
+template <class F>
+static void with_panel_variant(const GemmParams& p, F&& f) {
+  using std::integral_constant;
+  const auto folded = [&](auto EM, auto ACT) { p.lnst_in ? f(EM, ACT, std::true_type{}) : f(EM, ACT, std::false_type{}); };
+  if (p.emode == E_RESID) f(integral_constant<int, E_RESID>{}, integral_constant<int, ACT_NONE>{}, std::false_type{});
+  else if (p.emode == E_QKV) folded(integral_constant<int, E_QKV>{}, integral_constant<int, ACT_NONE>{});
+  else if (p.act == ACT_GELU) folded(integral_constant<int, E_STORE>{}, integral_constant<int, ACT_GELU>{});
+  else if (p.act == ACT_RELU) folded(integral_constant<int, E_STORE>{}, integral_constant<int, ACT_RELU>{});
+  else folded(integral_constant<int, E_STORE>{}, integral_constant<int, ACT_NONE>{});
+}
+
 hipError_t launch_panel_gemm(const GemmParams& p, hipStream_t st) {
   const int nch = p.N / PBN, npan = (p.M + PBM - 1) / PBM;
   const int U = nch * npan;
   const int G = U < cu_count() ? U : cu_count();
   const dim3 g(G), b(512);
-  if (knob(KNOB_PANEL32) && (p.emode == E_STORE || p.emode == E_QKV)) {
-    if (p.emode == E_QKV) {
-      if (p.lnst_in) hipLaunchKernelGGL((panel32_kernel<E_QKV, ACT_NONE, true>), g, b, 0, st, p, nch, npan);
-      else hipLaunchKernelGGL((panel32_kernel<E_QKV, ACT_NONE, false>), g, b, 0, st, p, nch, npan);
-    } else if (p.lnst_in) {
-      if (p.act == ACT_GELU) hipLaunchKernelGGL((panel32_kernel<E_STORE, ACT_GELU, true>), g, b, 0, st, p, nch, npan);
-      else if (p.act == ACT_RELU) hipLaunchKernelGGL((panel32_kernel<E_STORE, ACT_RELU, true>), g, b, 0, st, p, nch, npan);
-      else hipLaunchKernelGGL((panel32_kernel<E_STORE, ACT_NONE, true>), g, b, 0, st, p, nch, npan);
+  const bool p32 = knob(KNOB_PANEL32) && (p.emode == E_STORE || p.emode == E_QKV);
+  with_panel_variant(p, [&](auto EM, auto ACT, auto FOLD) {
+    constexpr int em = decltype(EM)::value, act = decltype(ACT)::value;
+    constexpr bool fold = decltype(FOLD)::value;
+    if (p32) {
+      if constexpr (em != E_RESID) hipLaunchKernelGGL((panel32_kernel<em, act, fold>), g, b, 0, st, p, nch, npan);
     } else {
-      if (p.act == ACT_GELU) hipLaunchKernelGGL((panel32_kernel<E_STORE, ACT_GELU, false>), g, b, 0, st, p, nch, npan);
-      else if (p.act == ACT_RELU) hipLaunchKernelGGL((panel32_kernel<E_STORE, ACT_RELU, false>), g, b, 0, st, p, nch, npan);
-      else hipLaunchKernelGGL((panel32_kernel<E_STORE, ACT_NONE, false>), g, b, 0, st, p, nch, npan);
+      hipLaunchKernelGGL((panel_gemm_kernel<em, act, fold>), g, b, 0, st, p, nch, npan);
     }
-    return hipGetLastError();
-  }
-  if (p.emode == E_RESID) {
-    hipLaunchKernelGGL((panel_gemm_kernel<E_RESID, ACT_NONE, false>), g, b, 0, st, p, nch, npan);
-  } else if (p.emode == E_QKV) {
-    if (p.lnst_in) hipLaunchKernelGGL((panel_gemm_kernel<E_QKV, ACT_NONE, true>), g, b, 0, st, p, nch, npan);
-    else hipLaunchKernelGGL((panel_gemm_kernel<E_QKV, ACT_NONE, false>), g, b, 0, st, p, nch, npan);
-  } else if (p.lnst_in) {
-    if (p.act == ACT_GELU) hipLaunchKernelGGL((panel_gemm_kernel<E_STORE, ACT_GELU, true>), g, b, 0, st, p, nch, npan);
-    else if (p.act == ACT_RELU) hipLaunchKernelGGL((panel_gemm_kernel<E_STORE, ACT_RELU, true>), g, b, 0, st, p, nch, npan);
-    else hipLaunchKernelGGL((panel_gemm_kernel<E_STORE, ACT_NONE, true>), g, b, 0, st, p, nch, npan);
-  } else {
-    if (p.act == ACT_GELU) hipLaunchKernelGGL((panel_gemm_kernel<E_STORE, ACT_GELU, false>), g, b, 0, st, p, nch, npan);
-    else if (p.act == ACT_RELU) hipLaunchKernelGGL((panel_gemm_kernel<E_STORE, ACT_RELU, false>), g, b, 0, st, p, nch, npan);
-    else hipLaunchKernelGGL((panel_gemm_kernel<E_STORE, ACT_NONE, false>), g, b, 0, st, p, nch, npan);
-  }
+  });
   return hipGetLastError();
 }
 

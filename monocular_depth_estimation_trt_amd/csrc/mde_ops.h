@@ -154,9 +154,8 @@ hipError_t launch_splitk_resid(const float* P, int S, int M, int N, const float*
 // second half of the E_STORE split-K path
 hipError_t launch_splitk_store(const float* P, int S, const GemmParams& p, hipStream_t st);
 
+// routes p (gemm_route.h: validation and the choice of kernel) and launches it
 hipError_t launch_gemm(const GemmParams& p, hipStream_t st);
-// slices launch_gemm's E_STORE split-K policy picks for p (1 = no split)
-int gemm_store_split_slices(const GemmParams& p);
 
 // Direct 3x3 conv with an LDS halo patch (conv.hip); launch_gemm routes
 // A_CONV3 / A_CONV3_UP problems here when conv_direct_supported().

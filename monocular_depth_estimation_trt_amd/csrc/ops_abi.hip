@@ -4,9 +4,11 @@
 // (gemm_params.h), kernels and dispatch policy in the launchers.
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <string>
 
 #include "engine_internal.h"
+#include "gemm_route.h"
 
 using namespace mde;
 
@@ -21,6 +23,22 @@ static int op_status(hipError_t e, const char* what) {
   return MDE_OK;
 }
 #define OP_RET(call, what) return op_status((call), what)
+
+int mde_debug_last_gemm_route(char* buf, size_t n) {
+  static const char* const kKind[] = {"none", "tile", "split_store", "split_resid", "conv_direct", "panel", "gemm256"};
+  const GemmRoute& r = gemm_last_route();
+  if (!buf) return fail(MDE_ERR_ARG, "mde_debug_last_gemm_route: null buffer");
+  int len;
+  if (r.kind == ROUTE_TILE || r.kind == ROUTE_SPLIT_STORE || r.kind == ROUTE_SPLIT_RESID)
+    len = snprintf(buf, n, "kind=%s bm=%d bn=%d wm=%d wn=%d bk=%d stages=%d slices=%d fused=%d resize_first=%d",
+                   kKind[r.kind], r.bm, r.bn, r.wm, r.wn, r.bk, r.stages, r.slices, r.fused, r.resize_first);
+  else if (r.kind == ROUTE_CONV_DIRECT)
+    len = snprintf(buf, n, "kind=%s resize_first=%d", kKind[r.kind], r.resize_first);
+  else
+    len = snprintf(buf, n, "kind=%s", kKind[r.kind >= 0 && r.kind <= ROUTE_GEMM256 ? r.kind : 0]);
+  if (len < 0 || (size_t)len >= n) return fail(MDE_ERR_ARG, "mde_debug_last_gemm_route: buffer too small");
+  return MDE_OK;
+}
 
 int mde_op_patch_prep_u8(const unsigned char* img, int batch, int h, int w, float scale, const float* mean3,
                          const float* std3, void* patches, void* st) {

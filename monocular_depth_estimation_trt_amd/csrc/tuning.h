@@ -29,10 +29,10 @@ enum Knob : int {
   // whenever legal).  test_gemm256_modes_match
   KNOB_GEMM256,
   // 4-deep LDS ring for small-grid 64^2 tiles (1: on).
-  // test_gemm_small_grid_variants_bit_exact
+  // test_gemm_small_grid_variants_bit_exact, test_deep64_ring (op level, the two routes)
   KNOB_DEEP64,
   // 8 waves on small-grid 128^2 tiles (1: on).
-  // test_gemm_small_grid_variants_bit_exact
+  // test_gemm_small_grid_variants_bit_exact, test_linear_strided, test_residual_splitk (op level, the two routes)
   KNOB_W8SMALL,
   // persistent 64 -> 64 channel direct conv with LDS-resident weights (0 off,
   // 1: 16 x 16-pixel tiles on 8 waves, 2: 8 x 16 on 4 waves).

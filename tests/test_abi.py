@@ -91,6 +91,24 @@ def test_tuning_switches(lib_path):
         _lib.set_tuning("lnfold", 7)
 
 
+def test_last_gemm_route_before_any_launch(lib_path):
+    """mde_debug_last_gemm_route on a new thread (the record is per thread):
+    no launch yet, and the buffer checks (include/mde.h)."""
+    import threading
+    from monocular_depth_estimation_trt_amd import _lib
+    got = {}
+
+    def fresh_thread():
+        got["route"] = _lib.last_gemm_route()
+        got["rc"] = (_lib.lib().mde_debug_last_gemm_route(ctypes.create_string_buffer(4), 4),
+                     _lib.lib().mde_debug_last_gemm_route(None, 0))
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert got == {"route": {"kind": "none"}, "rc": (1, 1)}, got
+
+
 def _run_py(code, env=None):
     import subprocess
     import sys

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from gpu_util import close, conv_w, nchw, nhwc, op, pad_w, ptr, stream, vt_perm
+from monocular_depth_estimation_trt_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
@@ -110,6 +111,12 @@ def test_panel_gemm_bit_exact(gpu, case):
     boundaries inside every panel)."""
     from monocular_depth_estimation_trt_amd import _lib
     k = 384
+
+    def assert_panel_or_bk32(panel):
+        """The last launch took the panel kernel, or the 128^2 BK 32 tiles it replaces."""
+        r = _lib.last_gemm_route()
+        assert r["kind"] == "panel" if panel else (r["kind"], r["bm"], r["bn"], r["bk"]) == ("tile", 128, 128, 32), r
+
     if case.startswith("resid"):
         # proj over the f16 residual stream: xh must match bit for bit; the
         # LN partials of the rows written sum the same 32 f16 values in
@@ -127,6 +134,7 @@ def test_panel_gemm_bit_exact(gpu, case):
             with _lib.tuning(panel=panel):
                 op("mde_op_linear_residual_f16", ptr(a), k, ptr(wp), wp.shape[1], m, n, k, ptr(b), ptr(ls), ptr(xh), n,
                    ptr(part), stream())
+            assert _lib.last_gemm_route()["kind"] == ("panel" if panel else "tile"), _lib.last_gemm_route()
             res.append((xh, part))
         d = (res[0][0].float() - res[1][0].float()).abs()
         assert torch.equal(res[0][0], res[1][0]), \
@@ -152,6 +160,7 @@ def test_panel_gemm_bit_exact(gpu, case):
                        k, act, ptr(out), n, stream())
                 else:
                     op("mde_op_linear", ptr(x), k, ptr(wp), wp.shape[1], m, n, k, ptr(b), act, ptr(out), n, stream())
+            assert_panel_or_bk32(panel)
             outs.append(out)
         assert torch.isfinite(outs[0]).all(), case
         d = (outs[0].float() - outs[1].float()).abs()
@@ -189,6 +198,7 @@ def test_panel_gemm_bit_exact(gpu, case):
             else:
                 op("mde_op_qkv", ptr(a), ptr(wp), wp.shape[1], ptr(b), B, T, H, Tp, 0.125, ptr(q), ptr(kk), ptr(vt),
                    stream())
+        assert_panel_or_bk32(panel)
         res.append((q, kk, vt))
     for name, x0, x1 in zip("q k vt".split(), res[0], res[1]):
         d = (x0.float() - x1.float()).abs()
@@ -674,8 +684,19 @@ def test_conv3x3_splitk(gpu, B, h, w, cin, cout, stride, relu_in, act, nres):
         op("mde_op_conv3x3_ws", ptr(xg), B, h, w, cin, ptr(wp), wp.shape[1], cout, stride, relu_in, ptr(bg), act,
            ptr(rg[0]), ptr(rg[1]), ptr(out), ptr(ws if cap else None), cap, C.byref(sl), stream())
         assert (sl.value > 1) == (cap > 0), f"split slices {sl.value} with workspace {cap}"
+        r = _lib.last_gemm_route()
+        if cap:  # the slices on 64^2 tiles + the reduce launch ("splitk_fused" is off by default)
+            assert (r["kind"], r["bm"], r["bn"], r["slices"], r["fused"]) == ("split_store", 64, 64, sl.value, 0), r
+        else:    # the direct conv, or the implicit-GEMM tiles (stride 2, small wide maps)
+            assert r["kind"] in ("conv_direct", "tile") and r.get("slices", 1) == 1, r
         close(nchw(out), ref, 1e-2, 1e-2, f"conv3x3 split {sl.value} {h}x{w} {cin}->{cout} s{stride}")
         got.append(out.float())
+    with _lib.tuning(splitk=0):  # the switch off: the workspace is not used
+        out = torch.empty(B, ho, wo, cout, dtype=torch.float16, device=gpu)
+        op("mde_op_conv3x3_ws", ptr(xg), B, h, w, cin, ptr(wp), wp.shape[1], cout, stride, relu_in, ptr(bg), act,
+           ptr(rg[0]), ptr(rg[1]), ptr(out), ptr(ws), ws.numel(), C.byref(sl), stream())
+    assert sl.value == 1 and _lib.last_gemm_route()["kind"] in ("conv_direct", "tile"), _lib.last_gemm_route()
+    assert torch.equal(out.float(), got[0]), "splitk = 0 must run the unsplit route"
     # the split only reassociates the fp32 sum
     assert (got[0] - got[1]).abs().max().item() < 2e-2
 
@@ -692,7 +713,16 @@ def test_linear_splitk(gpu, m, n, k, act):
     op("mde_op_linear_ws", ptr(f16(a, gpu)), k, ptr(wp), wp.shape[1], m, n, k, ptr(b.to(gpu)), act, ptr(out), n,
        ptr(ws), ws.numel(), C.byref(sl), stream())
     assert sl.value > 1 or k < 512, f"expected a split, got {sl.value}"
+    split = _lib.last_gemm_route()
+    assert (split["kind"], split["slices"]) == (("split_store" if sl.value > 1 else "tile"), sl.value), split
     close(out, ref, 1e-2, 1e-2, f"linear split {sl.value} {m}x{n}x{k} act{act}")
+    with _lib.tuning(splitk=0):  # the switch off: one launch of whole-K tiles
+        op("mde_op_linear_ws", ptr(f16(a, gpu)), k, ptr(wp), wp.shape[1], m, n, k, ptr(b.to(gpu)), act, ptr(out), n,
+           ptr(ws), ws.numel(), C.byref(sl), stream())
+    plain = _lib.last_gemm_route()
+    assert sl.value == 1 and (plain["kind"], plain["slices"]) == ("tile", 1), plain
+    assert (plain != split) == (k >= 512), (plain, split)
+    close(out, ref, 1e-2, 1e-2, f"linear unsplit {m}x{n}x{k} act{act}")
 
 
 @pytest.mark.parametrize("B,sh,sw,uh,uw,cin,cout", [(1, 10, 10, 19, 19, 64, 32), (2, 16, 12, 28, 21, 32, 64),
@@ -843,6 +873,8 @@ def test_gemm256_modes_match(gpu, M, N, K, act):
             out = torch.empty(M, N, dtype=torch.float16, device=gpu)
             op("mde_op_linear", ptr(ag), K, ptr(wp), wp.shape[1], M, N, K, ptr(bg), act, ptr(out), N, stream())
             torch.cuda.synchronize()
+        kind = _lib.last_gemm_route()["kind"]
+        assert kind == {0: "tile", 2: "gemm256"}.get(mode, kind), (mode, _lib.last_gemm_route())
         close(out, ref, 1e-2, 1e-2, f"linear gemm256={mode} {M}x{N}x{K}")
         outs.append(out.float().cpu())
     assert torch.allclose(outs[0], outs[2], rtol=2e-3, atol=2e-3), (outs[0] - outs[2]).abs().max()

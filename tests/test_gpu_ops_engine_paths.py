@@ -129,6 +129,13 @@ def test_linear_strided(gpu, route, m, n, k, act, switches):
     with _lib.tuning(**switches):
         op("mde_op_linear", ptr(strided_a(a16, 8, gpu)), k + 8, ptr(wp), wp.shape[1], m, n, k, ptr(b.to(gpu)), act,
            ptr(out), n + 8, stream())
+    r = _lib.last_gemm_route()
+    want = {"64^2 tiles": dict(kind="tile", bm=64, bn=64),
+            "128^2 tiles, BK 32": dict(kind="tile", bm=128, bn=128, wm=2, wn=2, bk=32),
+            "128^2 tiles, 8 waves": dict(kind="tile", bm=128, bn=128, wm=2, wn=4, bk=64),
+            "128^2 tiles, 4 waves": dict(kind="tile", bm=128, bn=128, wm=2, wn=2, bk=64),
+            "gemm256": dict(kind="gemm256"), "panel kernel": dict(kind="panel")}[route]
+    assert {f: r.get(f) for f in want} == want, (route, r)
     close(out[:m, :n], act64(base, act), 1e-2, 1e-2, f"linear {route} {m}x{n}x{k}")
     assert_guard(out, m, 0, n, f"linear {route}")
 
@@ -151,6 +158,8 @@ def test_linear_lnfold_strided(gpu, m, n, k, act):
     out = guarded(m, n + 8, torch.float16, gpu)
     op("mde_op_linear_lnfold", ptr(x.to(gpu)), ptr(ln_partials_ref(x).float().to(gpu)), 1e-6, ptr(wgp), wgp.shape[1],
        ptr(c1.to(gpu)), ptr(c2.to(gpu)), m, n, k, act, ptr(out), n + 8, stream())
+    r = _lib.last_gemm_route()
+    assert (r["kind"], r["bm"], r["bn"], r["bk"]) == (("tile", 64, 64, 64) if m == 300 else ("tile", 128, 128, 32)), r
     close(out[:m, :n], ref, 1e-2, 1.5e-2, f"linear_lnfold ldo {m}x{n}x{k}")
     assert_guard(out, m, 0, n, "linear_lnfold")
 
@@ -229,6 +238,8 @@ def check_linear_res(gpu, m, n, k, gap, combos, act=2, ws=None):
                     o, S = linear_res(gpu, p, act, res0, rows, relu, res1, ldo, ws, cnt, ws.numel())
                     o2, _ = linear_res(gpu, p, act, res0, rows, relu, res1, ldo, ws, cnt, ws.numel())
                 assert S > 1, f"{what}: expected a split, got {S} slices"
+                r = _lib.last_gemm_route()
+                assert (r["kind"], r["slices"], r["fused"]) == ("split_store", S, fused), (what, r)
                 # the two-kernel form leaves S planes of M x N partial sums in ws, the fused form S slots of
                 # 64 x 64 per tile: which of the two ran
                 tiles = -(-m // 64) * -(-n // 64)
@@ -374,6 +385,7 @@ def test_conv_res0_relu(gpu, route, B, h, w, cin, cout, stride, nres, split):
     if not split:
         out = guarded(m, cout, torch.float16, gpu)
         conv_res(gpu, geo, xg, wg, bg, rg[0], 1, rg[1], None, out)
+        assert _lib.last_gemm_route()["kind"] == ("conv_direct" if route == "direct" else "tile"), _lib.last_gemm_route()
         outs = [out]
     else:
         ws = torch.empty(1 << 20, dtype=torch.float32, device=gpu)
@@ -385,6 +397,8 @@ def test_conv_res0_relu(gpu, route, B, h, w, cin, cout, stride, nres, split):
             with _lib.tuning(splitk_fused=fused):
                 S = conv_res(gpu, geo, xg, wg, bg, rg[0], 1, rg[1], None, out, ws, cnt)
             assert S > 1, f"{what}: expected a split, got {S}"
+            r = _lib.last_gemm_route()
+            assert (r["kind"], r["slices"], r["fused"]) == ("split_store", S, fused), (what, r)
             tiles = -(-m // 64) * -(-cout // 64)
             assert written(ws) == (S * tiles * 4096 if fused else S * m * cout), (what, fused, written(ws))
             assert int(cnt.abs().max()) == 0, f"{what}: counters not left zero"
@@ -451,6 +465,9 @@ def test_conv_res1_up(gpu, case, B, h, w, cin, cout, sh, sw, with_res0, split, f
         scratch = guarded(m, cout, torch.float16, gpu)
         S = conv_res(gpu, geo, xg, wg, bg, r0g, 0, scratch, (ug, sh, sw), out, ws)
         assert (S > 1) == split, f"{what}: {S} slices"
+        r = _lib.last_gemm_route()  # the direct conv reads res1_up itself; every other route has it resized first
+        assert (r["kind"], r["resize_first"]) == (("split_store", 1) if split else
+                                                  ("conv_direct", int(not fold or case == "wide"))), (what, r)
         close(out[:m], ref, 1e-2, 1e-2, what)
         assert_guard(out, m, 0, cout, what)
         assert_guard(scratch, m, 0, cout, what + " (res1 buffer)")
@@ -633,6 +650,14 @@ def test_residual_splitk(gpu, route, m, n, k, switches, tiles, area, f16):
             with _lib.tuning(splitk_fused=fused):
                 x, part = resid_split(gpu, p, x0g, f16, 4, ws, cnt)
                 x2, part2 = resid_split(gpu, p, x0g, f16, 4, ws, cnt)
+            r = _lib.last_gemm_route()
+            want = {"64^2 slices": dict(kind="split_resid", bm=64, bn=64, fused=fused),
+                    "narrow tile": dict(kind="tile", bm=32, bn=64, stages=4, slices=1),
+                    "64^2 slices, narrow off": dict(kind="split_resid", bm=64, bn=64, fused=fused),
+                    "128^2 x 4 slices, 8 waves": dict(kind="split_resid", bm=128, bn=128, wn=4, slices=4, fused=fused),
+                    "128^2 x 4 slices, 4 waves": dict(kind="split_resid", bm=128, bn=128, wn=2, slices=4, fused=fused),
+                    }[route]
+            assert {f: r.get(f) for f in want} == want and (tiles == 0 or r["slices"] > 1), (what, fused, r)
             # which form ran: S planes of M x N partial sums, or S slots of a tile's area per tile
             nw = written(ws)
             if tiles == 0:
@@ -648,6 +673,7 @@ def test_residual_splitk(gpu, route, m, n, k, switches, tiles, area, f16):
                 assert torch.equal(part, part2), f"{what} fused {fused}: second call's partials differ"
             res.append((x, part))
         unsplit, upart = resid_split(gpu, p, x0g, f16, 0, None, None)
+        assert (_lib.last_gemm_route()["kind"], _lib.last_gemm_route()["slices"]) == ("tile", 1), _lib.last_gemm_route()
     assert torch.equal(res[0][0], res[1][0]), f"{what}: fused split differs from slices + reduce kernel"
     if f16:
         cells = n // 32 * m * 2

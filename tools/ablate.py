@@ -113,12 +113,13 @@ VARIANTS = {
     # same box: ViT-L B=1 3.19 -> 3.32 ms; qkv 0.612 -> 0.702, fc1 0.626 ->
     # 0.696 ms per forward)
     "gemm_wide_small": ("gemm.hip", [
-        ("""        if (w8small(big)) return run<128, 128, 2, 4, AM, EM>(p, st);""",
-         """        if (w8small(big)) {
-          const long long t2 = (long long)((p.M + 255) / 256) * ((p.N + 127) / 128);
-          if (t2 <= 256 && p.M >= 256) return run<256, 128, 4, 2, AM, EM, 32>(p, st);
-          return run<128, 128, 2, 4, AM, EM>(p, st);
-        }""", 1)]),
+        ("""    return dense && (em == E_STORE || em == E_QKV) && w8small(big) ? T128_W8 : T128;""",
+         """    if (dense && (em == E_STORE || em == E_QKV) && w8small(big))
+      return tiles(p.M, p.N, 256, 128) <= 256 && p.M >= 256 ? T256x128_BK32 : T128_W8;
+    return T128;""", 1),
+        # (the 256 x 128 tile built for the dense stores and qkv as well)
+        ("""    {256, 128, 4, 2, 32, 0, {mR, 0, 0}, {0, 0}},""",
+         """    {256, 128, 4, 2, 32, 0, {mS | mQ | mR, 0, 0}, {0, 0}},""", 1)]),
     # GEMM main loop only: the epilogue returns unless a NaN appears (r02's
     # MDE_EXP_NOEPI, profiles/r02_v10_epilogue_cost_*)
     "gemm_noepi": ("gemm.hip", [
