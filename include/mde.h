@@ -461,6 +461,50 @@ int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, co
                        int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
                        float z_lo, float z_hi, void* records, size_t records_bytes, int* counts, void* ws,
                        size_t ws_bytes, void* stream);
+/* Depth evaluation (added to ABI 11 without a new version number, as the point cloud was): the per-image
+ * call sequence of reference tools/evaluate_gt.py:555-583 over core/gt.py (orientation, align, metrics), on
+ * the device.  pred and gt are fp32 [batch][h][w] (pred: the output of mde_op_depth_postprocess /
+ * mde_op_dp_postprocess; gt in metres), mask is uint8 [batch][h][w], nonzero = measured.  policy: 0 none,
+ * 1 scale, 2 scale_shift.  max_depth <= 0: no range limit.  out is a device double[batch][16]:
+ *   0 status   0 scored; 1 fewer than two fit pixels; 2 scale_shift underdetermined (constant prediction)
+ *   1 n_fit    pixels the fit used (0 under policy none)
+ *   2 scale    NaN where nothing was fitted (policy none, status != 0)
+ *   3 shift    NaN unless policy scale_shift fitted one
+ *   4 n        pixels scored
+ *   5 abs_rel  6 rmse  7 log10  8 delta1  9 delta2  10 delta3     (NaN when n == 0)
+ *   11 orientation (Pearson correlation of pred and gt; NaN when undefined)
+ *   12 n_mask  pixels of m below (what separates the reference's two "fewer than two pixels" messages)
+ *   13..15 written as 0
+ * Per image, every per-pixel operation in float64 with one rounding per operation (x * s + t rounds twice):
+ *   m = mask && gt > 0
+ *   orientation: over m && isfinite(pred), from n, Sa, Sb, Saa, Sbb, Sab (a = pred, b = gt):
+ *     saa = Saa - Sa * Sa / n, sbb and sab likewise, sab / sqrt(saa * sbb); NaN when n < 2 or saa <= 0 or sbb <= 0
+ *   fit, scale: over m (narrowed to finite pred when fit_finite_only), s = Spg / max(Spp, 1e-12) where a
+ *     NaN Spp stays NaN; aligned = pred * s.  Without fit_finite_only one non-finite pred under m makes s NaN.
+ *   fit, scale_shift: over m && isfinite(pred), and pred > 0 unless pred_is_inverse; x = pred if inverse else
+ *     1 / pred, y = 1 / gt; d = n * Sxx - Sx * Sx, s = (n * Sxy - Sx * Sy) / d, t = (Sy - s * Sx) / n;
+ *     over the whole frame disp = x * s + t (x = NaN for pred <= 0 when not inverse),
+ *     aligned = disp > 1e-8 ? 1 / disp : +inf
+ *   fit, none: aligned = pred
+ *   status 1 when n_fit < 2, status 2 when |d| < 1e-12; then n = 0 and slots 5..10 are NaN
+ *   metrics: over m && isfinite(aligned), and gt <= max_depth when a limit is given; p = max(aligned, 1e-6),
+ *     ratio = max(p / g, g / p); n, mean |p - g| / g, sqrt(mean (p - g)^2), mean |log10 p - log10 g|, and
+ *     the fractions ratio < 1.25, < 1.5625, < 1.953125
+ * Four kernels.  A workgroup owns MDE_DEPTH_EVAL_TILE consecutive pixels of one image, whatever the grid
+ * or the card, and writes that tile's partial sums to ws; one workgroup per image adds them in a fixed
+ * order.  No workgroup waits on another's writes and there are no floating-point atomics: the same 128
+ * bytes per image on every run.  ws: mde_op_depth_eval_ws_bytes(batch, h, w) bytes of device scratch,
+ * 8-byte aligned (0 is returned for sizes the op refuses).  The kernels are held to
+ * monocular_depth_estimation_trt_amd/evaluate.py:score_np within the summation-order tolerance derived in
+ * DESIGN.md, "Scoring against ground truth".  mde_op_depth_eval only enqueues on `stream` (no allocation,
+ * no synchronisation, no host read: capturable).  MDE_ERR_ARG, before any device call: a null pointer; a
+ * non-positive size; a policy outside 0..2; h * w of 2^31 - 256 or more; batch > 65535; NaN max_depth; ws
+ * null or ws_bytes too small; out or ws not 8-byte aligned. */
+#define MDE_DEPTH_EVAL_TILE 1024
+size_t mde_op_depth_eval_ws_bytes(int batch, int h, int w);
+int mde_op_depth_eval(const float* pred, const float* gt, const unsigned char* mask, int batch, int h, int w,
+                      int policy, int pred_is_inverse, int fit_finite_only, float max_depth, double* out, void* ws,
+                      size_t ws_bytes, void* stream);
 /* Depth Pro pyramid patches (upstream DepthProEncoder._create_pyramid + _split, reference engine input
  * "input"): fp32 NCHW image [batch][3][size][size] (size = 4 * 384) -> f16 patch-embed rows
  * [nseq * batch * 576][768] ((c, py, px) order), sequence s = patch * batch + image with the 25

@@ -220,6 +220,14 @@ size_t point_cloud_ws_bytes(int B, int h, int w, int step);
 hipError_t launch_point_cloud(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
                               int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
                               float z_lo, float z_hi, void* records, int* counts, void* ws, hipStream_t st);
+// depth_eval.hip: fp32 prediction and ground truth [B][h][w] and a uint8 mask -> double out[B][16]
+// (include/mde.h, mde_op_depth_eval: fit status and parameters, the metrics, the orientation);
+// ws = depth_eval_ws_bytes() of 8-byte aligned scratch.  Enqueues four kernels, nothing else.  No
+// argument checks here: the ABI wrapper in ops_abi.hip holds the only copy of the limits
+size_t depth_eval_ws_bytes(int B, int h, int w);
+hipError_t launch_depth_eval(const float* pred, const float* gt, const unsigned char* mask, int B, int h, int w,
+                             int policy, int pred_is_inverse, int fit_finite_only, float max_depth, double* out,
+                             void* ws, hipStream_t st);
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H,
                              int W, int ph, int pw, int T, int D, hipStream_t st, h16* Xh = nullptr,
                              float* lnst = nullptr, const float* cls_st = nullptr, float* P32 = nullptr);

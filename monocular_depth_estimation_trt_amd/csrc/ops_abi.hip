@@ -156,6 +156,36 @@ int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, co
          "mde_op_point_cloud");
 }
 
+namespace {
+const char* depth_eval_geometry_error(int batch, int h, int w) {
+  if (batch < 1 || h < 1 || w < 1) return "batch and sizes must be positive";
+  if ((long long)h * w >= 0x80000000LL - 256) return "a plane of 2^31 - 256 pixels or more";
+  if (batch > 65535) return "batch > 65535";
+  return nullptr;
+}
+}  // namespace
+
+size_t mde_op_depth_eval_ws_bytes(int batch, int h, int w) {
+  if (depth_eval_geometry_error(batch, h, w)) return 0;
+  return depth_eval_ws_bytes(batch, h, w);
+}
+
+int mde_op_depth_eval(const float* pred, const float* gt, const unsigned char* mask, int batch, int h, int w,
+                      int policy, int pred_is_inverse, int fit_finite_only, float max_depth, double* out, void* ws,
+                      size_t ws_bytes, void* st) {
+  const char* why = (!pred || !gt || !mask || !out) ? "null pointer" : depth_eval_geometry_error(batch, h, w);
+  if (!why && (policy < 0 || policy > 2)) why = "policy must be 0 (none), 1 (scale) or 2 (scale_shift)";
+  if (!why && !(max_depth == max_depth)) why = "max_depth is NaN";
+  if (!why && (!ws || ws_bytes < depth_eval_ws_bytes(batch, h, w)))
+    why = "needs ws of mde_op_depth_eval_ws_bytes()";
+  if (!why && ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(out)) & 7))
+    why = "out and ws must be 8-byte aligned";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_depth_eval: ") + why);
+  OP_RET(launch_depth_eval(pred, gt, mask, batch, h, w, policy, pred_is_inverse != 0, fit_finite_only != 0, max_depth,
+                           out, ws, (hipStream_t)st),
+         "mde_op_depth_eval");
+}
+
 int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
   if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
   DpPyramid pyr;

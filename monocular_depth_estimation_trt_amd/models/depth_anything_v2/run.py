@@ -13,6 +13,7 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
         [--image photo.npy|photo.jpg] [--host-preprocess]
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
         [--ply out.ply --f-px F [--ply-step N]]
+        [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed -- taken through the
@@ -38,6 +39,17 @@ driver's clamp [1e-3, 1e3] dropped.  There is no FOV head: `--f-px` (focal
 length in pixels at the source size) is required.  Relative models (the
 relative checkpoints, depth_anything_ac, distill_any_depth) are refused:
 relative depth is not turned into metres.
+
+`--gt DEPTH.npy --gt-mask MASK.npy` scores the map against measured ground
+truth of the same size (the reference's tools/evaluate_gt.py:555-583 over its
+core/gt.py), on the device (evaluate.DeviceEval) from the map the device
+post-process left there -- for distill_any_depth, which has no post-process,
+the engine's output binding.  The alignment comes from the model's spec.json:
+`depth_scale` metric -> none, relative -> scale and shift fitted in disparity,
+`output_form` saying which way round the output runs.  One `[MDET] gt : ...`
+line is printed and the result written as JSON (`--gt-out`, default
+<out-dir>/<model>_gt.json); `--max-depth` drops ground truth beyond the
+sensor's range.
 """
 
 import argparse
@@ -46,7 +58,7 @@ import time
 
 import numpy as np
 
-from monocular_depth_estimation_trt_amd import bench, common, spec, weights
+from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, weights
 from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
@@ -88,6 +100,7 @@ def build_parser(model="depth_anything_v2", mc=None):
                     help="write the point cloud (binary PLY; colours from --image) of the metric depth; needs --f-px")
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
     ap.add_argument("--f-px", type=float, default=None, help="with --ply: focal length in pixels at the source size")
+    evaluate.add_gt_arguments(ap)
     return ap
 
 
@@ -133,7 +146,8 @@ def _device_preprocess(img, model, input_hw, input_format, mem, stream):
 
 
 def main(argv=None, model="depth_anything_v2"):
-    mc = spec.model_config_of(spec.load(model))
+    model_spec = spec.load(model)
+    mc = spec.model_config_of(model_spec)
     input_h, input_w = mc["input_hw"]
     a = build_parser(model, mc).parse_args(argv)
     u8 = a.input_format == "uint8_nhwc"
@@ -143,9 +157,12 @@ def main(argv=None, model="depth_anything_v2"):
         raise SystemExit("--host-preprocess needs --image")
     if a.ply:
         _check_ply(a, mc)
+    gt_policy = evaluate.check_gt_arguments(a, model_spec, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
     if a.src_hw is None:
         a.src_hw = list(img.shape[:2]) if img is not None else [2268, 3024]
+    gt_hw = (input_h, input_w) if mc["postprocess"] == "none" else tuple(a.src_hw)  # the size of the scored map
+    gt_maps = evaluate.load_gt_arguments(a, gt_hw) if gt_policy else None
     if a.ply and img is not None and tuple(a.src_hw) != img.shape[:2]:
         raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
     if u8 and a.engine.endswith("_fp16.mdeng"):
@@ -185,6 +202,8 @@ def main(argv=None, model="depth_anything_v2"):
                                  stream=stream), warmup=a.warmup, iterations=a.iterations)
         if mc["postprocess"] == "none":   # distill_any_depth: the 518x518 map as is (its onnx2trt.py:98-100)
             depth = outs[0].reshape(output_shape)[0].copy()
+            if gt_policy:  # no post-process: the engine's output binding is the map
+                evaluate.driver_score(a, model, gt_policy, gt_maps, outputs[0].device, gt_hw, stream)
         elif a.host_postprocess:
             depth = postprocess(outs[0].reshape(output_shape), a.src_hw)
         else:  # the engine's output is still in outputs[0].device
@@ -195,6 +214,8 @@ def main(argv=None, model="depth_anything_v2"):
                                        f_px=a.f_px, z_lo=1e-3, z_hi=1e3)
                     print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {a.src_hw[0]}x{a.src_hw[1]} step "
                           f"{a.ply_step} -> {a.ply} : {ms:0.3f} ms, {n} points")
+                if gt_policy:
+                    evaluate.driver_score(a, model, gt_policy, gt_maps, pp.mem.device, gt_hw, stream)
         bench.record(model, samples, warmup=a.warmup, precision="fp16", profile="bench",
                      variant="u8" if u8 else "single",
                      input_h=input_h, input_w=input_w, engine_path=a.engine, outputs={"depth": depth},

@@ -12,6 +12,7 @@
         [--source synthetic:depth_pro | DepthPro.safetensors] [--image photo.npy|photo.jpg]
         [--input x.npy] [--src-hw H W] [--f-px F] [--host-preprocess] [--host-postprocess]
         [--ply out.ply] [--ply-step N]
+        [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed.  It is normalised and
@@ -35,6 +36,14 @@ photo (no colours with `--input` or the synthetic image).  It runs on the
 device (pointcloud.DevicePointCloud) on the depth map and the focal length the
 device post-process left there, drops depths outside [1e-4, 1e4] and downloads
 the PLY records; `--ply-step N` keeps every N-th pixel on both axes.
+
+`--gt DEPTH.npy --gt-mask MASK.npy` scores the metric depth against measured
+ground truth of the source size (the reference's tools/evaluate_gt.py:555-583
+over its core/gt.py), on the device (evaluate.DeviceEval) from the map the
+device post-process left there, with the alignment the spec's `depth_scale`
+earns (metric: none).  One `[MDET] gt : ...` line is printed and the result
+written as JSON (`--gt-out`, default <out-dir>/depth_pro_gt.json);
+`--max-depth` drops ground truth beyond the sensor's range.
 """
 
 import argparse
@@ -44,7 +53,7 @@ import time
 
 import numpy as np
 
-from monocular_depth_estimation_trt_amd import bench, common, spec, weights_depth_pro
+from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, weights_depth_pro
 from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
                                                                stream_synchronize)
 from monocular_depth_estimation_trt_amd.pointcloud import device_ply
@@ -84,6 +93,7 @@ def build_parser(model="depth_pro", size=None):
     ap.add_argument("--ply", default="", metavar="PATH",
                     help="write the point cloud (binary PLY; colours from --image) of the metric depth")
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
+    evaluate.add_gt_arguments(ap)
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out-dir", default=os.path.join(os.getcwd(), "reports", "bench"))
@@ -131,12 +141,13 @@ def _device_preprocess(img, size, mem, stream):
         ev.free()
 
 
-def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None):
+def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None):
     """DepthProDevicePostprocess on the output bindings in place, timed with
     hipEvents (kernel + D2H of the depth map and the focal length); `ply` =
     (path, step, photo or None): then the point cloud of the map, while it is
     still on the device, with the focal length the post-process used (the
-    fourth result, pointcloud.device_ply's; else None)."""
+    fourth result, pointcloud.device_ply's; else None); `score`: called with
+    the map's device pointer while it is still there (--gt)."""
     if f_px is None and len(outputs) < 2:
         raise SystemExit("this engine has no fov_deg output: pass --f-px")
     ev = _Events(stream)
@@ -153,6 +164,8 @@ def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None):
                 path, step, img = ply
                 cloud = device_ply(path, pp.mem.device, *src_hw, stream, step=step, img_bgr=img,
                                    d_f_px=pp.f_px.device, f_px=f_px, z_lo=1e-4, z_hi=1e4)
+            if score:
+                score(pp.mem.device)
             return depth, f, ms, cloud
     finally:
         ev.free()
@@ -173,6 +186,7 @@ def main(argv=None, model="depth_pro"):
                          "--host-postprocess")
     if a.ply and a.ply_step < 1:
         raise SystemExit("--ply-step must be positive")
+    gt_policy = evaluate.check_gt_arguments(a, s, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
     if img is not None and not a.host_preprocess:
         x = None  # filled on the device, below
@@ -190,6 +204,7 @@ def main(argv=None, model="depth_pro"):
             how = "host, torch resize of a normalised tensor"
         print(f"[MDET] preprocess ({how}) {H}x{W} -> {size}x{size} : {(time.perf_counter() - t0) * 1e3:0.3f} ms")
     src_hw = tuple(a.src_hw) if a.src_hw else (H, W)
+    gt_maps = evaluate.load_gt_arguments(a, src_hw) if gt_policy else None
     if a.ply and img is not None and src_hw != img.shape[:2]:
         raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
     output_shapes = (1, 1, size, size)
@@ -213,8 +228,10 @@ def main(argv=None, model="depth_pro"):
             print(f"[MDET] postprocess (host, torch) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{(time.perf_counter() - t0) * 1e3:0.3f} ms")
         else:  # the engine's outputs are still in outputs[*].device
+            score = (lambda d_map: evaluate.driver_score(a, model, gt_policy, gt_maps, d_map, src_hw, stream)) if gt_policy \
+                else None
             depth, f_px, ms, cloud = _device_postprocess(outputs, size, src_hw, a.f_px, stream,
-                                                         ply=(a.ply, a.ply_step, img) if a.ply else None)
+                                                         ply=(a.ply, a.ply_step, img) if a.ply else None, score=score)
             print(f"[MDET] postprocess (device, kernel + D2H, hipEvents) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{ms:0.3f} ms")
             if cloud:
