@@ -58,7 +58,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "mde_device.h"
+#include "lds_pipe.h"
 #include "mde_ops.h"
 #include "tuning.h"
 
@@ -74,14 +74,6 @@ constexpr int QW = 32;            // queries per wave (one 32-column MFMA block)
 #define ATTN_RING 2               // K/V^T ring depth (tiles; R-1 in flight while one is computed)
 #endif
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-MDE_DEV f32x16 mfma32(const f16x8& a, const f16x8& b, const f32x16& c) {
-  // D[32x32] += A[32x16] B[16x32]; lane l: A[l&31][8(l>>5)+j], B[8(l>>5)+j][l&31];
-  // D col l&31, row (r&3) + 8(r>>2) + 4(l>>5) for register r
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
 // Deferred rescale (cdna_hip_programming.md 5.5 T13): the running max moves
 // only when a block's max exceeds it by more than RESCALE_T (log2 units), so
 // p = exp2(S - m_run) <= 2^RESCALE_T = 256 -- exact in f16's range, and the
@@ -94,28 +86,6 @@ constexpr float RESCALE_T = 8.f;
 // parities, and (row >> 1) & 7 spreads each parity's 8 rows over 8 chunks:
 // every 16-lane group touches 64 distinct banks
 MDE_DEV int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-MDE_DEV float swap_max(float x) {  // max over lanes l and l ^ 32
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-MDE_DEV float swap_sum(float x) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-template <int N>
-MDE_DEV void wait_vm_n() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Workgroup barrier that leaves LDS-DMA in flight: own LDS reads retired,
-// raw s_barrier, and compiler fences so no LDS access moves across it.
-MDE_DEV void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 MDE_DEV unsigned pack2(float a, float b) {
   typedef f16 f16x2 __attribute__((ext_vector_type(2)));
@@ -220,8 +190,8 @@ attn_fwd_kernel(const f16* __restrict__ q, const f16* __restrict__ k, const f16*
       if (8 % NWQ && g >= 8) break;
       const int row = g * 8 + lrow;
       const int lc = pc ^ ((row >> 1) & 7);
-      __builtin_amdgcn_global_load_lds(kb + (size_t)(kt * KT + row) * 64 + lc * 8, sK + g * 8 * 128, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(vb + (size_t)row * Tpad + kt * KT + lc * 8, sV + g * 8 * 128, 16, 0, 0);
+      glds16(kb + (size_t)(kt * KT + row) * 64 + lc * 8, sK + g * 8 * 128);
+      glds16(vb + (size_t)row * Tpad + kt * KT + lc * 8, sV + g * 8 * 128);
     }
   };
 
@@ -502,7 +472,7 @@ attn_fwd_kernel(const f16* __restrict__ q, const f16* __restrict__ k, const f16*
 // groups, so the rare rescale's row max reduces with v_permlane32_swap +
 // v_permlane16_swap; the row sums come from two more MFMAs with an all-ones
 // A operand (below).
-MDE_DEV int swz16(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
+MDE_DEV int swz16(int row, int chunk) { return row * 128 + (swz7(row, chunk) << 4); }
 
 MDE_DEV float grp4_max(float x) {  // max over lanes (l & 15) + 16 g, g = 0..3
   auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -573,8 +543,8 @@ MDE_DEV void attn16_body(const f16* __restrict__ q, const f16* __restrict__ k, c
       const int gg = wave + i * NWQ;  // 8-row group
       const int row = gg * 8 + lrow;
       const int lc = pc ^ lrow;      // swz16: row & 7 == lrow
-      __builtin_amdgcn_global_load_lds(kb + (size_t)(kt * KT + row) * 64 + lc * 8, sK + gg * 8 * 128, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(vb + (size_t)row * Tpad + kt * KT + lc * 8, sV + gg * 8 * 128, 16, 0, 0);
+      glds16(kb + (size_t)(kt * KT + row) * 64 + lc * 8, sK + gg * 8 * 128);
+      glds16(vb + (size_t)row * Tpad + kt * KT + lc * 8, sV + gg * 8 * 128);
     }
   };
 

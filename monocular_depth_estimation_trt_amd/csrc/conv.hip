@@ -17,7 +17,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "mde_device.h"
+#include "lds_pipe.h"
 #include "mde_ops.h"
 #include "tile_epilogue.h"
 #include "tuning.h"
@@ -49,31 +49,6 @@ namespace {
 
 __device__ __attribute__((aligned(64))) f16 g_zero_conv[64];
 
-MDE_DEV void glds16c(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-MDE_DEV void wait_vmc() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// The same LDS-DMA (64-bit vaddr form) issued from inline asm: hipcc does not
-// see it, so its ds_read waits in the DMA's shadow stay counted (lgkmcnt(N))
-// instead of lgkmcnt(0) -- it models a pending FLAT LDS-DMA as an
-// out-of-order lgkm event.  The caller counts the DMA itself (vmcnt) and
-// orders LDS accesses around it with "memory" asm.  M0 is written and
-// restored inside the statement (compiler-reserved).
-MDE_DEV void glds16_asm(const void* src, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(lds_dst)
-               : "memory");
-}
-// workgroup barrier without __syncthreads()'s fence (which drains vmcnt, i.e.
-// also the epilogue's global stores): own LDS accesses retired, s_barrier
-MDE_DEV void lds_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 typedef f16 f16x2c __attribute__((ext_vector_type(2)));
 
 // a + (b - a) * w on halves 2J, 2J+1: v_pk_add_f16 (neg) + v_pk_fma_f16.  The
@@ -102,7 +77,7 @@ MDE_DEV f16x8 lerp8(const f16x8& a, const f16x8& b, f16 w) {
 
 template <int CK>
 MDE_DEV int cpch(int pix, int lc) {
-  if constexpr (CK == 64) return lc ^ (pix & 7);
+  if constexpr (CK == 64) return swz7(pix, lc);
   else return lc ^ ((pix >> 1) & 3);
 }
 
@@ -182,7 +157,7 @@ __global__ void __launch_bounds__(WM * WN * 64)
         const int iy = iy0 + py, ix = ix0 + px;
         const bool ok = pp < PHW && iy >= 0 && iy < IH && ix >= 0 && ix < IW;
         const f16* src = ok ? img + ((size_t)iy * p.cw + ix) * p.cc + cbase + lch * 8 : g_zero_conv;
-        glds16c(src, sP + q * RWP * ROWB);
+        glds16(src, sP + q * RWP * ROWB);
       }
     } else {
       // one thread per (virtual pixel, 4 channel chunks): its source indices
@@ -236,7 +211,7 @@ __global__ void __launch_bounds__(WM * WN * 64)
     const int chunk = step / 9, t = step - (step / 9) * 9;
     const int k0 = t * p.cc + chunk * CK;
     char* dst = sB0 + buf * BSTAGE;
-    for (int q = wave; q < BINS; q += NW) glds16c(wbase + (size_t)q * RWP * p.ldw + k0, dst + q * RWP * ROWB);
+    for (int q = wave; q < BINS; q += NW) glds16(wbase + (size_t)q * RWP * p.ldw + k0, dst + q * RWP * ROWB);
   };
 
   // pre-activation ReLU of the staged (glds) patch, once per pixel in LDS
@@ -263,7 +238,7 @@ __global__ void __launch_bounds__(WM * WN * 64)
     load_patch(0);
 #pragma unroll
     for (int t = 0; t < 9; ++t) load_b(t, t);
-    wait_vmc();
+    wait_vm_n<0>();
     __syncthreads();
     if (!UP && p.relu_in) {
       relu_patch();
@@ -300,7 +275,7 @@ __global__ void __launch_bounds__(WM * WN * 64)
     load_patch(chunk);
     const int step0 = chunk * 9;
     load_b(step0, step0 & 1);
-    wait_vmc();
+    wait_vm_n<0>();
     __syncthreads();
     if (!UP && p.relu_in) {
       relu_patch();
@@ -331,7 +306,7 @@ __global__ void __launch_bounds__(WM * WN * 64)
 #pragma unroll
           for (int j = 0; j < TN; ++j) acc[i][j] = mfma16x16x32(fb[j], fa[i], acc[i][j]);
       }
-      wait_vmc();
+      wait_vm_n<0>();
       __syncthreads();
     }
   }
@@ -468,7 +443,7 @@ conv64p_kernel(const GemmParams p) {
   // ---- the weight set, once
   for (int q = wave; q < 9 * 64 / RWP; q += NW) {
     const int tap = q >> 3, n = (q & 7) * RWP + lrow;
-    glds16c(reinterpret_cast<const f16*>(p.W) + (size_t)n * p.ldw + tap * 64 + lch * 8, smem + WOFF + q * RWP * ROWB);
+    glds16(reinterpret_cast<const f16*>(p.W) + (size_t)n * p.ldw + tap * 64 + lch * 8, smem + WOFF + q * RWP * ROWB);
   }
   // ASM: the in-loop prefetch (glds16_asm); the prologue's patch uses the
   // builtin, drained by __syncthreads()'s vmcnt(0) before the loop
@@ -487,7 +462,7 @@ conv64p_kernel(const GemmParams p) {
       if constexpr (decltype(asm_tag)::value)
         glds16_asm(src, __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dst + q * RWP * ROWB)));
       else
-        glds16c(src, dst + q * RWP * ROWB);
+        glds16(src, dst + q * RWP * ROWB);
     }
   };
   // MODE 0: ReLU of a landed patch, in place (callers barrier before and after)
@@ -529,11 +504,11 @@ conv64p_kernel(const GemmParams p) {
     bias[j] = p.bias ? *reinterpret_cast<const float4*>(p.bias + j * 16 + (lane >> 4) * 4) : float4{0.f, 0.f, 0.f, 0.f};
 
   load_patch(t, 0, std::false_type{});
-  wait_vmc();
+  wait_vm_n<0>();
   __syncthreads();
   if constexpr (MODE == 0) {
     if (MDE_CONVP_RELU_PASS) relu_patch(0);
-    lds_sync();
+    lds_barrier();
   }
 
   // one tile: MFMAs on patch buffer BUF while the next tile's patch lands in
@@ -600,8 +575,8 @@ conv64p_kernel(const GemmParams p) {
     // tile's residual loads, all issued before the MFMAs, too) -- after the
     // barrier every wave's DMAs and patch reads are done: the epilogue may
     // stage in this buffer and the next tile read the other
-    wait_vmc();
-    lds_sync();
+    wait_vm_n<0>();
+    lds_barrier();
     if constexpr (MODE == 0) {
       if (MDE_CONVP_RELU_PASS && tn < tend) relu_patch(BUF ^ 1);
     }
@@ -673,7 +648,7 @@ conv64p_kernel(const GemmParams p) {
       }
     }
     if (tn >= tend) return true;
-    lds_sync();  // staging reads retired before the next prefetch overwrites them; the next patch is ReLU'd (stores stay in flight)
+    lds_barrier();  // staging reads retired before the next prefetch overwrites them; the next patch is ReLU'd (stores stay in flight)
     t = tn;
     return false;
   };
@@ -810,7 +785,7 @@ upconv_kernel(const GemmParams p) {
     for (int q = wave; q < WROWS / 16; q += 8) {
       const int tc = q >> 1, n = (q & 1) * 16 + lrow;
       const int tp = tc / NCH, c = tc - (tc / NCH) * NCH;
-      glds16c(reinterpret_cast<const f16*>(p.W) + (size_t)n * p.ldw + tp * p.cc + c * 32 + lch * 8, sW + q * 16 * 64);
+      glds16(reinterpret_cast<const f16*>(p.W) + (size_t)n * p.ldw + tp * p.cc + c * 32 + lch * 8, sW + q * 16 * 64);
     }
   }
 
@@ -906,7 +881,7 @@ upconv_kernel(const GemmParams p) {
     int vt;
     asm volatile("v_mov_b32 %0, %1" : "=v"(vt) : "v"(tid));
     const int vl = vt & 63;
-    wait_vmc();  // this item's pass-H operands (and, first time, the weights) landed
+    wait_vm_n<0>();  // this item's pass-H operands (and, first time, the weights) landed
     h_commit(vt);
     __syncthreads();  // H complete; every wave done with the previous item's MFMAs / staging
     if constexpr (SW) {
@@ -957,8 +932,8 @@ upconv_kernel(const GemmParams p) {
     if constexpr (SW) {
       // this wave's weight DMAs landed: only the next item's 2 HI pass-H
       // loads, issued after them, may still be in flight
-      if (tn < tend) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * HI) : "memory");
-      else wait_vmc();
+      if (tn < tend) wait_vm_n<2 * HI>();
+      else wait_vm_n<0>();
     }
     __syncthreads();
     // ---- 9 taps x one 32-deep k-step of chunk c

@@ -112,22 +112,7 @@ __global__ void __launch_bounds__(256) merge_tokens_kernel(const float* __restri
   for (int i = 0; i < PER; ++i) v[i] = xr[i * 64 + lane];
   f16* yr = y + (size_t)pix * D;
   if constexpr (LN) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) s += v[i];
-    const float mean = wave_sum(s) * (1.0f / D);
-    float qv = 0.f;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const float d = v[i] - mean;
-      qv += d * d;
-    }
-    const float rstd = rsqrtf(wave_sum(qv) * (1.0f / D) + eps);
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int c = i * 64 + lane;
-      yr[c] = (f16)((v[i] - mean) * rstd * g[c] + bt[c]);
-    }
+    row_layernorm(v, lane, g, bt, eps, [&](int c, float o) { yr[c] = (f16)o; });
   } else {
 #pragma unroll
     for (int i = 0; i < PER; ++i) yr[i * 64 + lane] = (f16)v[i];
@@ -184,21 +169,12 @@ hipError_t launch_merge_tokens(const float* x, h16* y, const float* g, const flo
   if (pix <= 0) return hipSuccess;
   dim3 grid((unsigned)((pix + 3) / 4)), block(256);
   f16* yo = reinterpret_cast<f16*>(y);
-#define MDE_MERGE(PER)                                                                                   \
-  case PER * 64:                                                                                         \
-    if (ln) hipLaunchKernelGGL((merge_tokens_kernel<PER, true>), grid, block, 0, st, x, yo, g, b, m, eps);  \
-    else hipLaunchKernelGGL((merge_tokens_kernel<PER, false>), grid, block, 0, st, x, yo, g, b, m, eps);  \
-    break;
-  switch (D) {
-    MDE_MERGE(2)
-    MDE_MERGE(4)
-    MDE_MERGE(6)
-    MDE_MERGE(12)
-    MDE_MERGE(16)
-    default: return hipErrorInvalidValue;
-  }
-#undef MDE_MERGE
-  return hipGetLastError();
+  return with_row_per<2, 4, 6, 12, 16>(D, [&](auto P) {
+    constexpr int PER = decltype(P)::value;
+    if (ln) hipLaunchKernelGGL((merge_tokens_kernel<PER, true>), grid, block, 0, st, x, yo, g, b, m, eps);
+    else hipLaunchKernelGGL((merge_tokens_kernel<PER, false>), grid, block, 0, st, x, yo, g, b, m, eps);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_fov_final(const h16* in, const float* w, float bias, int K, int B, float* out, hipStream_t st) {

@@ -34,26 +34,10 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const XT* __restrict__ x
   }
   const XT* xr = x + (size_t)row * D;
   float v[PER];
-  float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    v[i] = (float)xr[i * 64 + lane];
-    s += v[i];
-  }
-  const float mean = wave_sum(s) * (1.0f / D);
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const float d = v[i] - mean;
-    q += d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+  for (int i = 0; i < PER; ++i) v[i] = (float)xr[i * 64 + lane];
   YT* yr = y + (size_t)orow * D;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int c = i * 64 + lane;
-    yr[c] = (YT)((v[i] - mean) * rstd * g[c] + bt[c]);
-  }
+  row_layernorm(v, lane, g, bt, eps, [&](int c, float o) { yr[c] = (YT)o; });
 }
 
 // f16 residual rows: 16 lanes per row, 4 rows per wave, 16 rows per
@@ -360,20 +344,13 @@ hipError_t launch_layernorm(const float* x, h16* y, const float* g, const float*
   dim3 grid((rows + 3) / 4), block(256);
   f16* yo = reinterpret_cast<f16*>(y);
   const f16* xf = reinterpret_cast<const f16*>(xh);
-#define MDE_LN(PER)                                                                                                 \
-  if (xh) hipLaunchKernelGGL((layernorm_h8_kernel<PER * 8>), dim3((rows + 15) / 16), block, 0, st, xf, yo, g, b, rows, \
-                             eps, T, skip_cls);                                                                      \
-  else hipLaunchKernelGGL((layernorm_kernel<PER, float>), grid, block, 0, st, x, yo, g, b, rows, eps, T, skip_cls);
-  switch (D) {
-    case 128: MDE_LN(2) break;
-    case 256: MDE_LN(4) break;
-    case 384: MDE_LN(6) break;
-    case 768: MDE_LN(12) break;
-    case 1024: MDE_LN(16) break;
-    default: return hipErrorInvalidValue;
-  }
-#undef MDE_LN
-  return hipGetLastError();
+  return with_row_per<2, 4, 6, 12, 16>(D, [&](auto P) {
+    constexpr int PER = decltype(P)::value;
+    if (xh) hipLaunchKernelGGL((layernorm_h8_kernel<PER * 8>), dim3((rows + 15) / 16), block, 0, st, xf, yo, g, b, rows,
+                               eps, T, skip_cls);
+    else hipLaunchKernelGGL((layernorm_kernel<PER, float>), grid, block, 0, st, x, yo, g, b, rows, eps, T, skip_cls);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_layernorm32(const float* x, float* y, const float* g, const float* b, int rows, int D, float eps,
@@ -381,15 +358,11 @@ hipError_t launch_layernorm32(const float* x, float* y, const float* g, const fl
   if (T <= 0 || (skip_cls && T < 2)) return hipErrorInvalidValue;
   if (rows <= 0) return hipSuccess;
   const dim3 grid((rows + 3) / 4), block(256);
-  switch (D) {
-    case 128: hipLaunchKernelGGL((layernorm_kernel<2, float, float>), grid, block, 0, st, x, y, g, b, rows, eps, T, skip_cls); break;
-    case 256: hipLaunchKernelGGL((layernorm_kernel<4, float, float>), grid, block, 0, st, x, y, g, b, rows, eps, T, skip_cls); break;
-    case 384: hipLaunchKernelGGL((layernorm_kernel<6, float, float>), grid, block, 0, st, x, y, g, b, rows, eps, T, skip_cls); break;
-    case 768: hipLaunchKernelGGL((layernorm_kernel<12, float, float>), grid, block, 0, st, x, y, g, b, rows, eps, T, skip_cls); break;
-    case 1024: hipLaunchKernelGGL((layernorm_kernel<16, float, float>), grid, block, 0, st, x, y, g, b, rows, eps, T, skip_cls); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_row_per<2, 4, 6, 12, 16>(D, [&](auto P) {
+    hipLaunchKernelGGL((layernorm_kernel<decltype(P)::value, float, float>), grid, block, 0, st, x, y, g, b, rows, eps, T,
+                       skip_cls);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H, int W, int ph,

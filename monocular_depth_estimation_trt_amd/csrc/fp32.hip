@@ -39,19 +39,12 @@
 // two-stage ring.
 #include <cstdint>
 
-#include "mde_device.h"
+#include "lds_pipe.h"
 #include "mde_ops.h"
 
 namespace mde {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-MDE_DEV void glds16f(const void* src, void* lds) { __builtin_amdgcn_global_load_lds(src, lds, 16, 0, 0); }
-MDE_DEV void wait_vm32() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-MDE_DEV int pch32(int r, int lc) { return lc ^ (r & 7); }
 
 // padding taps of the implicit-im2col A read this (a glds lane cannot be
 // masked, it can be redirected)
@@ -77,7 +70,7 @@ __global__ void __launch_bounds__(256) gemm32_kernel(const Gemm32Params p) {
   const int m0 = tm * BM, n0 = tn * BN;
 
   const int lrow = lane / CH;
-  const int lch = pch32(lrow, lane % CH);
+  const int lch = swz7(lrow, lane % CH);
   const float* arow[APASS];
   int iy0[APASS], ix0[APASS];
   bool rv[APASS];
@@ -116,7 +109,7 @@ __global__ void __launch_bounds__(256) gemm32_kernel(const Gemm32Params p) {
       // column 0 of its row instead (finite, and inside the row even when K < 32)
       const int ka = k0 + lch * 4 < p.K ? k0 : -lch * 4;
 #pragma unroll
-      for (int i = 0; i < APASS; ++i) glds16f(arow[i] + ka, sb + (wave + i * NW) * RW * ROWB);
+      for (int i = 0; i < APASS; ++i) glds16(arow[i] + ka, sb + (wave + i * NW) * RW * ROWB);
     } else {
       const bool kv = k0 + lch * 4 < p.K;
       const int ky = tap / 3, kx = tap - (tap / 3) * 3;
@@ -125,7 +118,7 @@ __global__ void __launch_bounds__(256) gemm32_kernel(const Gemm32Params p) {
         const int iy = iy0[i] + ky, ix = ix0[i] + kx;
         const bool ok = rv[i] && kv && iy >= 0 && iy < p.ch && ix >= 0 && ix < p.cw;
         const float* src = ok ? arow[i] + ((size_t)iy * p.cw + ix) * p.cc + cch : g_zero32;
-        glds16f(src, sb + (wave + i * NW) * RW * ROWB);
+        glds16(src, sb + (wave + i * NW) * RW * ROWB);
       }
       cch += 32;
       while (cch >= p.cc) {
@@ -135,7 +128,7 @@ __global__ void __launch_bounds__(256) gemm32_kernel(const Gemm32Params p) {
     }
 #pragma unroll
     for (int i = 0; i < BPASS; ++i)
-      glds16f(wrow + (size_t)i * NW * RW * p.ldw + k0, sb + BM * ROWB + (wave + i * NW) * RW * ROWB);
+      glds16(wrow + (size_t)i * NW * RW * p.ldw + k0, sb + BM * ROWB + (wave + i * NW) * RW * ROWB);
   };
 
   f32x4 acc[TM][TN];
@@ -154,7 +147,7 @@ __global__ void __launch_bounds__(256) gemm32_kernel(const Gemm32Params p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int r = wm * TM * 16 + i * 16 + (lane & 15);
-        fa[i] = *reinterpret_cast<const f32x4*>(sA + r * ROWB + pch32(r, lc) * 16);
+        fa[i] = *reinterpret_cast<const f32x4*>(sA + r * ROWB + swz7(r, lc) * 16);
         if constexpr (AM == A_CONV3) {
           if (p.relu_in) {
 #pragma unroll
@@ -165,7 +158,7 @@ __global__ void __launch_bounds__(256) gemm32_kernel(const Gemm32Params p) {
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int r = wn * TN * 16 + j * 16 + (lane & 15);
-        fb[j] = *reinterpret_cast<const f32x4*>(sB + r * ROWB + pch32(r, lc) * 16);
+        fb[j] = *reinterpret_cast<const f32x4*>(sB + r * ROWB + swz7(r, lc) * 16);
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t)
@@ -178,12 +171,12 @@ __global__ void __launch_bounds__(256) gemm32_kernel(const Gemm32Params p) {
   };
 
   issue(0, 0);
-  wait_vm32();
+  wait_vm_n<0>();
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
     if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);
     mma(kt & 1);
-    wait_vm32();
+    wait_vm_n<0>();
     __syncthreads();
   }
 
@@ -300,15 +293,6 @@ hipError_t run32(const Gemm32Params& p, hipStream_t st) {
 // through LDS (small grids: batch 1); NKG = 1: four query blocks.
 constexpr float RESCALE_T32 = 8.f;
 
-MDE_DEV float swap_max32(float x) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-MDE_DEV float swap_sum32(float x) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 template <int NKG>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4)))
 attn32_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
@@ -380,7 +364,7 @@ attn32_kernel(const float* __restrict__ q, const float* __restrict__ k, const fl
     float mx = sc[0];
 #pragma unroll
     for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
-    mx = swap_max32(mx);
+    mx = swap_max(mx);
     const bool first = blk == kb0;
     if (first || mx > m_run + RESCALE_T32) {
       const float mnew = first ? mx : fmaxf(mx, m_run);
@@ -460,7 +444,7 @@ attn32_kernel(const float* __restrict__ q, const float* __restrict__ k, const fl
   if (!active) return;
   const int qi = q0 + l31;
   if (qi >= T) return;
-  const float inv = 1.f / swap_sum32(l_run);
+  const float inv = 1.f / swap_sum(l_run);
   // lane holds O^T[dh = 32 db + (r & 3) + 8 (r >> 2) + 4 hh][qi]: 4 consecutive dh per group
   float* orow = o + ((size_t)b * T + qi) * ldo + hd * 64;
 #pragma unroll

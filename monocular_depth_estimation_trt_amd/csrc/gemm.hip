@@ -34,7 +34,7 @@
 #include <utility>
 
 #include "gemm_route.h"
-#include "mde_device.h"
+#include "lds_pipe.h"
 #include "mde_ops.h"
 #include "tile_epilogue.h"
 #include "tuning.h"
@@ -70,25 +70,6 @@ namespace {
 
 __device__ __attribute__((aligned(64))) f16 g_zero_line[64];  // zero-initialised module global
 
-MDE_DEV void glds16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-
-MDE_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-template <int N>
-MDE_DEV void wait_vm_n() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// Workgroup barrier that leaves LDS-DMA in flight (__syncthreads() would
-// also drain vmcnt): own LDS reads retired, raw s_barrier, compiler fences.
-MDE_DEV void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 // LDS tile geometry for a K-step of BK halves: rows of BK*2 bytes, 16-byte
 // chunks; one glds wave-instruction (64 lanes x 16 B) fills RW rows.
 template <int BK>
@@ -98,7 +79,7 @@ struct KGeo {
   static constexpr int RW = 64 / CH;        // rows per wave-instruction
   // physical chunk of logical chunk lc in row r (conflict-free ds_read_b128)
   static MDE_DEV int pch(int r, int lc) {
-    if constexpr (BK == 64) return lc ^ (r & 7);
+    if constexpr (BK == 64) return swz7(r, lc);
     else return lc ^ ((r >> 1) & 3);
   }
 };
@@ -416,14 +397,14 @@ __global__ void __launch_bounds__(WM * WN * 64) MDE_GEMM_WPE_ATTR
     issue(0, 0);
     commit_up(0);
     ln_partial_loads();
-    wait_vm();
+    wait_vm_n<0>();
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = kt & 1;
       if (kt + 1 < nk) issue(kt + 1, cur ^ 1);
       mma_stage(cur);
       if (kt + 1 < nk) commit_up(cur ^ 1);
-      wait_vm();
+      wait_vm_n<0>();
       __syncthreads();
     }
   } else {
@@ -476,7 +457,7 @@ __global__ void __launch_bounds__(WM * WN * 64) MDE_GEMM_WPE_ATTR
           __hip_atomic_store(d + 1, (u64)__float_as_uint(a[2]) | ((u64)__float_as_uint(a[3]) << 32), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_SYSTEM);
         }
-      wait_vm();  // this wave's slot stores have completed
+      wait_vm_n<0>();  // this wave's slot stores have completed
       __shared__ int s_last;
       __syncthreads();
       if (tid == 0) {
@@ -859,13 +840,6 @@ hipError_t gemm_route(const GemmParams& p, GemmRoute& r) {
 const GemmRoute& gemm_last_route() { return t_last_route; }
 
 namespace {
-
-// f(std::integral_constant<int, x>) for x in [0, N); any other x is an invalid argument
-template <int N, class F>
-hipError_t with_constant(int x, F&& f) {
-  if constexpr (N == 0) return hipErrorInvalidValue;
-  else return x == N - 1 ? f(std::integral_constant<int, N - 1>{}) : with_constant<N - 1>(x, f);
-}
 
 // gemm_kernel on r's row of the table with p's modes (fused: its fused split-K form), over r's tiles x slices
 hipError_t launch_tiles(const GemmRoute& r, const GemmParams& p, bool fused, hipStream_t st) {

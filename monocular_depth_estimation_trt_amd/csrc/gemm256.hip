@@ -30,7 +30,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "mde_device.h"
+#include "lds_pipe.h"
 #include "mde_ops.h"
 #include "tuning.h"
 #include "tile_epilogue.h"
@@ -48,22 +48,7 @@ constexpr int ROWB = BK * 2;         // 128 bytes per LDS row
 constexpr int TILE_B = 256 * ROWB;   // one operand tile, 32 KB
 constexpr int BUF_B = 2 * TILE_B;    // A + W
 
-MDE_DEV void g256_glds(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-
-MDE_DEV void g256_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-template <int N>
-MDE_DEV void g256_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-MDE_DEV int g256_off(int row, int lc) { return row * ROWB + ((lc ^ (row & 7)) << 4); }
+MDE_DEV int g256_off(int row, int lc) { return row * ROWB + (swz7(row, lc) << 4); }
 
 template <int EM>
 __global__ void __launch_bounds__(NW * 64) gemm256_kernel(const GemmParams p) {
@@ -107,12 +92,12 @@ __global__ void __launch_bounds__(NW * 64) gemm256_kernel(const GemmParams p) {
   auto issue_w = [&](int kt, int buf) {
     const int k0 = kt * BK;  // W is zero-padded to ldw >= K rounded up to 64
 #pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) g256_glds(Wb + (wsrc[r4] + k0), smem + buf * BUF_B + woff[r4]);
+    for (int r4 = 0; r4 < 4; ++r4) glds16(Wb + (wsrc[r4] + k0), smem + buf * BUF_B + woff[r4]);
   };
   auto issue_a = [&](int q, int kt, int buf) {
     const int k = kt * BK + lch * 8;
     const int kk = k < p.K ? k : 0;  // K tail: W is zero there, any finite A chunk of the row will do
-    g256_glds(Ab + (asrc[q] + kk), smem + buf * BUF_B + aoff[q]);
+    glds16(Ab + (asrc[q] + kk), smem + buf * BUF_B + aoff[q]);
   };
 
   // fragments: W blocks nb (rows 64 wc + 16 nb + l15), A blocks 2q+i (rows
@@ -187,26 +172,26 @@ __global__ void __launch_bounds__(NW * 64) gemm256_kernel(const GemmParams p) {
     }
     mfma_phase(I0{});
     read_a(b, 1);
-    g256_barrier();
+    lds_barrier();
     if (pre) issue_a(1, t + 2, b);
     mfma_phase(I1{});
     read_a(b, 2);
-    g256_barrier();
+    lds_barrier();
     if (pre) issue_a(2, t + 2, b);
     mfma_phase(I2{});
     read_a(b, 3);
     // K-tile t+1 (issued during tile t-1) must have landed before phase 3
     // reads it; the 7 glds of tile t+2 issued since stay in flight
-    if (pre) g256_vmcnt<7>();
-    else g256_vmcnt<0>();
-    g256_barrier();
+    if (pre) wait_vm_n<7>();
+    else wait_vm_n<0>();
+    lds_barrier();
     if (pre) issue_a(3, t + 2, b);
     mfma_phase(I3{});
     if (nxt) {
       read_w(b ^ 1);
       read_a(b ^ 1, 0);
     }
-    g256_barrier();
+    lds_barrier();
   };
 
   // prologue: tiles 0 and 1 in flight, tile 0 landed, its W + A quarter 0 read
@@ -217,14 +202,14 @@ __global__ void __launch_bounds__(NW * 64) gemm256_kernel(const GemmParams p) {
     issue_w(1, 1);
 #pragma unroll
     for (int q = 0; q < 4; ++q) issue_a(q, 1, 1);
-    g256_vmcnt<8>();
+    wait_vm_n<8>();
   } else {
-    g256_vmcnt<0>();
+    wait_vm_n<0>();
   }
-  g256_barrier();
+  lds_barrier();
   read_w(0);
   read_a(0, 0);
-  g256_barrier();  // every wave's reads of W / A quarter 0 retired before phase 0 refills them
+  lds_barrier();  // every wave's reads of W / A quarter 0 retired before phase 0 refills them
   for (int t = 0; t < nk; t += 2) {
     tile(t, I0{});
     if (t + 1 < nk) tile(t + 1, I1{});

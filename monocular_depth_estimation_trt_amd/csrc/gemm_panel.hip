@@ -42,7 +42,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "mde_device.h"
+#include "lds_pipe.h"
 #include "mde_ops.h"
 #include "tuning.h"
 
@@ -112,25 +112,7 @@ MDE_DEV void pglds_chunk(const char* base, unsigned off, unsigned lds) {
 }
 #undef PGLDS_SEG
 
-// s_waitcnt vmcnt(0) as an instruction the compiler's wait insertion sees
-// (an asm wait is opaque to it: loads it thinks pending at the loop head get
-// a vmcnt(0) at their first use in EVERY unit -- with the W chunk DMA issued
-// just before, that drained the ring each unit).  gfx9 simm16: vmcnt [3:0] +
-// [15:14] = 0, expcnt [6:4] = 7, lgkmcnt [11:8] = 15
-MDE_DEV void pwait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
-// s_waitcnt vmcnt(N) (N < 64; expcnt / lgkmcnt not waited), the same way
-template <int N>
-MDE_DEV void pwait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
-}
-
-// raw workgroup barrier: LDS-DMA stays in flight (__syncthreads would drain vmcnt)
-MDE_DEV void pbarrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// (the vmcnt waits below are lds_pipe.h's wait_vm_seen, the form hipcc's wait insertion sees)
 
 // target of the stores of rows >= M (keeps the epilogue branch-free, so it
 // stays in the MFMA stream's basic block)
@@ -608,7 +590,7 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
         //    load, so that count is strict by up to three substeps, never lax.
         load_panel(pnl);
         if (j == 0) {
-          pwait_vm<2 * PKS>();
+          wait_vm_seen<2 * PKS>();
         } else {
           PTRACE(93, 1)  // (no standalone epilogue in this form)
         }
@@ -625,7 +607,7 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
           epi_all(acc1);
           PTRACE(93, 1)
         } else {
-          pwait_vm<2 * PKS>();
+          wait_vm_seen<2 * PKS>();
         }
         if constexpr (FOLD) stats_merge(lst, lmean, lrstd);
       } else {
@@ -640,7 +622,7 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
           stats_load(pnl, lst);
           stats_merge(lst, lmean, lrstd);
         }
-        pwait_vm0();  // A and every issued chunk landed (once per panel)
+        wait_vm_seen<0>();  // A and every issued chunk landed (once per panel)
       }
       if (j > 0) {
         PTRACE(93, 2)
@@ -671,7 +653,7 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
       //    with 8 stores: vmcnt(16).
       auto step = [&](auto peel_tag, int jj, f32x4(&accC)[2][4], const f32x4(&accP)[2][4]) __attribute__((always_inline)) {
         constexpr int PEEL = decltype(peel_tag)::value;
-        pbarrier();
+        lds_barrier();
         PTRACE(jj, 0)
         if (jj + PLEAD < nu) issue(jj + PLEAD);
         const int cc = gunit(jj) - pnl * nch;
@@ -685,12 +667,12 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
         PTRACE(jj, 1)
         static_assert(!STREAM || PLEAD == 2, "streamed forms: the counts assume a 3-slot ring");
         if constexpr (EM == E_RESID) {
-          pwait_vm0();  // (its residual loads: consumed next unit)
+          wait_vm_seen<0>();  // (its residual loads: consumed next unit)
         } else if (XPEEL == 1 && jj == j0 + 1) {
-          if (jj + PLEAD < nu) pwait_vm<6 + 8>();
-          else pwait_vm<8>();
+          if (jj + PLEAD < nu) wait_vm_seen<6 + 8>();
+          else wait_vm_seen<8>();
         } else {
-          pwait_vm<8 * PLEAD>();
+          wait_vm_seen<8 * PLEAD>();
         }
         PTRACE(jj, 2)
       };
@@ -732,7 +714,7 @@ __global__ void __launch_bounds__(512) panel_gemm_kernel(const GemmParams p, int
     }
     epi_all(acc1);  // the last unit's epilogue
 #ifdef PX_TRACE
-    pwait_vm0();
+    wait_vm_seen<0>();
     PTRACE(90, 0)  // (kernel end, stores drained)
 #endif
   };
@@ -776,11 +758,6 @@ constexpr int P3KS = PK / 16;  // 32x32x16 k-steps per unit (24)
 #ifndef P3_OFF1
 #define P3_OFF1 12  // first epilogue k-step of waves 4-7 (waves 0-3: 0)
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-MDE_DEV f32x16 pmfma32(const f16x8& a, const f16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
 
 template <int EM, int ACT, bool FOLD>
 __global__ void __launch_bounds__(512) panel32_kernel(const GemmParams p, int nch, int npan) {
@@ -972,8 +949,8 @@ __global__ void __launch_bounds__(512) panel32_kernel(const GemmParams p, int nc
       // the previous unit's epilogue: group pairs q = 0..3 at k-steps OFF + 3 q
       const int rel = s - OFF;
       const bool ep = rel >= 0 && rel < 12 && (rel % 3) == 0;
-      accC[0] = pmfma32(wf[s & 1][0], af[s], accC[0]);
-      accC[1] = pmfma32(wf[s & 1][1], af[s], accC[1]);
+      accC[0] = mfma32(wf[s & 1][0], af[s], accC[0]);
+      accC[1] = mfma32(wf[s & 1][1], af[s], accC[1]);
       if (ep) epi_pair32(rel / 3, pnl, pc, accP, prstd, epi);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -1010,12 +987,12 @@ __global__ void __launch_bounds__(512) panel32_kernel(const GemmParams p, int nc
       float2 st[2][8];
       if constexpr (FOLD) stats_load(pnl, st);
       load_panel(pnl);
-      pwait_vm<P3KS>();
+      wait_vm_seen<P3KS>();
       if constexpr (FOLD) stats_merge(st, lmean, lrstd);
       PTRACE(j > 0 ? 94 : 92, 0)  // (trace: statistics landed)
       const int j0 = j;
       auto step = [&](int jj, f32x16(&accC)[2], const f32x16(&accP)[2]) __attribute__((always_inline)) {
-        pbarrier();
+        lds_barrier();
         PTRACE(jj, 0)
         if (jj + PLEAD < nu) issue(jj + PLEAD);
         const int cc = (u0 + jj) - pnl * nch;
@@ -1027,8 +1004,8 @@ __global__ void __launch_bounds__(512) panel32_kernel(const GemmParams p, int nc
         // end, chunk jj + 2's 6 DMAs
         static_assert(PLEAD == 2, "panel32: the counts below assume a 3-slot ring");
         PTRACE(jj, 1)
-        if (jj + PLEAD < nu) pwait_vm<4 + 6 + 4>();
-        else pwait_vm<4 + 4>();
+        if (jj + PLEAD < nu) wait_vm_seen<4 + 6 + 4>();
+        else wait_vm_seen<4 + 4>();
         PTRACE(jj, 2)
       };
       // the run's first unit peeled off the loop: its k-steps wait for their
@@ -1049,7 +1026,7 @@ __global__ void __launch_bounds__(512) panel32_kernel(const GemmParams p, int nc
       ppnl = pnl;
     }
     epi_all(acc1, ppnl);
-    pwait_vm0();
+    wait_vm_seen<0>();
     PTRACE(90, 0)  // (trace: kernel end, stores drained)
   };
   if (wave < 4) run(std::integral_constant<int, 0>{});

@@ -18,10 +18,54 @@ MDE_DEV f32x4 mfma16x16x32(const f16x8& a, const f16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+MDE_DEV f32x16 mfma32(const f16x8& a, const f16x8& b, const f32x16& c) {
+  // D[32x32] += A[32x16] B[16x32]; lane l: A[l&31][8(l>>5)+j], B[8(l>>5)+j][l&31];
+  // D col l&31, row (r&3) + 8(r>>2) + 4(l>>5) for register r
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+MDE_DEV float swap_max(float x) {  // max over lanes l and l ^ 32
+  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+MDE_DEV float swap_sum(float x) {  // sum over lanes l and l ^ 32
+  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
 MDE_DEV float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// LayerNorm of one row of D = 64 PER fp32 values by one wave: lane `lane`
+// holds columns i * 64 + lane in v[i] and hands column c's result to
+// store(c, value).  Two passes (mean, then the squared deviations), sums in
+// index order then wave_sum: every kernel that calls this gives the same bits
+// for the same row.  Compiled with the caller's contraction setting.
+template <int PER, class Store>
+MDE_DEV void row_layernorm(const float (&v)[PER], int lane, const float* __restrict__ g,
+                           const float* __restrict__ bt, float eps, Store&& store) {
+  constexpr int D = PER * 64;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) s += v[i];
+  const float mean = wave_sum(s) * (1.0f / D);
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const float d = v[i] - mean;
+    q += d * d;
+  }
+  const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int c = i * 64 + lane;
+    store(c, (v[i] - mean) * rstd * g[c] + bt[c]);
+  }
 }
 
 // GELU (exact-erf definition: nn.GELU() default, upstream DINOv2 Mlp) as

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace mde {
 
 typedef _Float16 h16;
@@ -282,5 +284,22 @@ hipError_t launch_qk_norm_rope(h16* q, h16* k, const float* qg, const float* qb,
                                hipStream_t st);
 hipError_t launch_tap_concat_ln(const float* xa, const float* xb, h16* y, const float* g, const float* b, int nseq,
                                 int T, int npre, int D, float eps, hipStream_t st);
+
+// ---- a run-time value as a template argument ----
+// f(std::integral_constant<int, x>) for x in [0, N); any other x is an invalid argument
+template <int N, class F>
+hipError_t with_constant(int x, F&& f) {
+  if constexpr (N == 0) return hipErrorInvalidValue;
+  else return x == N - 1 ? f(std::integral_constant<int, N - 1>{}) : with_constant<N - 1>(x, f);
+}
+// The wave-per-row kernels give each lane PER = D / 64 columns of a row:
+// f(std::integral_constant<int, PER>) for the PER of the launcher's list PERS
+// with D == 64 PER; any other width is an invalid argument (nothing launched)
+template <int PER, int... PERS, class F>
+hipError_t with_row_per(int D, F&& f) {
+  if (D == 64 * PER) return f(std::integral_constant<int, PER>{});
+  if constexpr (sizeof...(PERS) > 0) return with_row_per<PERS...>(D, f);
+  else return hipErrorInvalidValue;
+}
 
 }  // namespace mde

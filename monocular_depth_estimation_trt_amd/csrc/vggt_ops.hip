@@ -48,25 +48,9 @@ __global__ void __launch_bounds__(256) rows_layernorm_kernel(float* __restrict__
   const int seq = (int)(r / per_seq), t = row0 + (int)(r - (long long)seq * per_seq);
   float* xr = X + ((size_t)seq * T + t) * D;
   float v[PER];
-  float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    v[i] = xr[i * 64 + lane];
-    s += v[i];
-  }
-  const float mean = wave_sum(s) * (1.0f / D);
-  float qv = 0.f;
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const float d = v[i] - mean;
-    qv += d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(qv) * (1.0f / D) + eps);
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const int c = i * 64 + lane;
-    xr[c] = (v[i] - mean) * rstd * g[c] + bt[c];
-  }
+  for (int i = 0; i < PER; ++i) v[i] = xr[i * 64 + lane];
+  row_layernorm(v, lane, g, bt, eps, [&](int c, float o) { xr[c] = o; });
 }
 
 // q / k rows [BH][Tpad][64] f16; 8 lanes per row, lane c of the group owns
@@ -197,16 +181,10 @@ hipError_t launch_rows_layernorm(float* X, const float* g, const float* b, int n
   const long long rows = (long long)nseq * (T - row0);
   if (rows <= 0) return hipSuccess;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  switch (D) {
-    case 128: hipLaunchKernelGGL(rows_layernorm_kernel<2>, grid, block, 0, st, X, g, b, nseq, T, row0, eps); break;
-    case 256: hipLaunchKernelGGL(rows_layernorm_kernel<4>, grid, block, 0, st, X, g, b, nseq, T, row0, eps); break;
-    case 384: hipLaunchKernelGGL(rows_layernorm_kernel<6>, grid, block, 0, st, X, g, b, nseq, T, row0, eps); break;
-    case 512: hipLaunchKernelGGL(rows_layernorm_kernel<8>, grid, block, 0, st, X, g, b, nseq, T, row0, eps); break;
-    case 768: hipLaunchKernelGGL(rows_layernorm_kernel<12>, grid, block, 0, st, X, g, b, nseq, T, row0, eps); break;
-    case 1024: hipLaunchKernelGGL(rows_layernorm_kernel<16>, grid, block, 0, st, X, g, b, nseq, T, row0, eps); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_row_per<2, 4, 6, 8, 12, 16>(D, [&](auto P) {
+    hipLaunchKernelGGL(rows_layernorm_kernel<decltype(P)::value>, grid, block, 0, st, X, g, b, nseq, T, row0, eps);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_qk_norm_rope(h16* q, h16* k, const float* qg, const float* qb, const float* kg, const float* kb,
@@ -229,21 +207,10 @@ hipError_t launch_tap_concat_ln(const float* xa, const float* xb, h16* y, const 
   if (rows <= 0) return hipSuccess;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   f16* yo = reinterpret_cast<f16*>(y);
-#define MDE_TAPLN(PER)                                                                                          \
-  case PER * 64:                                                                                                \
-    hipLaunchKernelGGL((tap_concat_ln_kernel<PER>), grid, block, 0, st, xa, xb, yo, g, b, nseq, T, npre, eps); \
-    break;
-  switch (D) {
-    MDE_TAPLN(2)
-    MDE_TAPLN(4)
-    MDE_TAPLN(6)
-    MDE_TAPLN(8)
-    MDE_TAPLN(12)
-    MDE_TAPLN(16)
-    default: return hipErrorInvalidValue;
-  }
-#undef MDE_TAPLN
-  return hipGetLastError();
+  return with_row_per<2, 4, 6, 8, 12, 16>(D, [&](auto P) {
+    hipLaunchKernelGGL(tap_concat_ln_kernel<decltype(P)::value>, grid, block, 0, st, xa, xb, yo, g, b, nseq, T, npre, eps);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace mde

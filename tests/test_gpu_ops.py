@@ -542,6 +542,54 @@ def test_layernorm_f16_stream(gpu, D, skip):
     close(y, ref, 1e-2, 1e-2, f"layernorm_f16 D{D} skip{skip}")
 
 
+@pytest.mark.parametrize("B,G", [(1, 3), (3, 3)])
+@pytest.mark.parametrize("D", [128, 384, 1024])
+def test_row_layernorm_kernels_bit_identical(gpu, D, B, G):
+    """layernorm_kernel and merge_tokens_kernel<., true> share one row-LayerNorm
+    core: over one patch without padding the merge is the identity map over
+    the non-cls rows, so the two ops give the same bits (10 and 30 rows: the
+    last workgroup of 4 rows is partial)."""
+    T = G * G + 1
+    gen = torch.Generator().manual_seed(D * 100 + B * 10 + G)
+    x = (torch.randn(B * T, D, generator=gen) * 3 + 1.5).to(gpu)
+    g = (1 + 0.1 * torch.randn(D, generator=gen)).to(gpu)
+    b = (0.02 * torch.randn(D, generator=gen)).to(gpu)
+    y_ln = torch.zeros(B * (T - 1), D, dtype=torch.float16, device=gpu)
+    y_mg = torch.ones_like(y_ln)
+    op("mde_op_layernorm", ptr(x), ptr(y_ln), ptr(g), ptr(b), B * T, D, 1e-6, T, 1, stream())
+    op("mde_op_merge_tokens", ptr(x), B, T, D, 1, G, 0, 0, ptr(g), ptr(b), 1e-6, ptr(y_mg), stream())
+    torch.cuda.synchronize()
+    assert torch.equal(y_ln.view(torch.int16), y_mg.view(torch.int16))
+    ref = F.layer_norm(x.cpu(), (D,), g.cpu(), b.cpu(), 1e-6).reshape(B, T, D)[:, 1:].reshape(B * (T - 1), D)
+    close(y_ln, ref, 1e-2, 1e-2, f"row layernorm D{D} B{B} G{G}")
+
+
+def test_row_kernel_width_sets(gpu):
+    """The widths each launcher takes: 512 only where the VGGT depth head
+    needs it; a width outside a launcher's set fails on the host."""
+    from monocular_depth_estimation_trt_amd._lib import MDEError
+    D, G = 512, 2
+    T = G * G + 1
+    gen = torch.Generator().manual_seed(512)
+    xa = torch.randn(T, D, generator=gen) * 2 + 0.5
+    xb = torch.randn(T, D, generator=gen) * 0.5 - 1.0
+    g = 1 + 0.1 * torch.randn(2 * D, generator=gen)
+    b = 0.1 * torch.randn(2 * D, generator=gen)
+    xg, gg, bg = xa.to(gpu), g.to(gpu), b.to(gpu)
+    y = torch.zeros(T, 2 * D, dtype=torch.float16, device=gpu)
+    with pytest.raises(MDEError):
+        op("mde_op_layernorm", ptr(xg), ptr(y), ptr(gg), ptr(bg), T, D, 1e-6, T, 1, stream())
+    with pytest.raises(MDEError):
+        op("mde_op_merge_tokens", ptr(xg), 1, T, D, 1, G, 0, 0, ptr(gg), ptr(bg), 1e-6, ptr(y), stream())
+    torch.cuda.synchronize()
+    assert float(y.float().abs().max()) == 0.0  # nothing was launched
+    op("mde_op_tap_concat_ln", ptr(xg), ptr(xb.to(gpu)), 1, T, 1, D, ptr(gg), ptr(bg), 1e-5, ptr(y), stream())
+    ref = F.layer_norm(torch.cat([xa, xb], -1)[1:], (2 * D,), g, b, 1e-5)
+    err = (y[:T - 1].float().cpu() - ref).abs()
+    # f16 output: half an ulp is 2^-11 relative (the bound of test_tap_concat_ln_op)
+    assert float(err.max()) <= 2e-3 * float(ref.abs().max()) + 1e-3, float(err.max())
+
+
 @pytest.mark.parametrize("B,Hh,Ww", [(2, 98, 98), (1, 126, 182), (16, 518, 518), (48, 98, 140)])
 def test_patch_embed(gpu, B, Hh, Ww):
     """Patch gather (elementwise.hip patch_prep_kernel: one thread per image

@@ -50,18 +50,18 @@ VARIANTS = {
         ("for (int s = 0; s < QS; ++s) sc.v[s] = mfma32(kf, qf[s][st], sc.v[s]);",
          'for (int s = 0; s < QS; ++s) asm volatile("" :: "v"(kf), "v"(qf[s][st]));', 1)]),
     # attention: no K/V waits or barriers (LDS races: wrong values, timing only)
+    # (the file's own lds_barrier / wait_vm_n, which hide lds_pipe.h's inside its unnamed namespace)
     "attn_nosync": ("attention.hip", [
-        ("""MDE_DEV void lds_barrier() {
+        ("namespace {\n\nconstexpr int KT = 64;", """namespace {
+
+MDE_DEV void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}""", """MDE_DEV void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}""", 1),
-        ("""MDE_DEV void wait_vm_n() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}""", """MDE_DEV void wait_vm_n() {
-}""", 1)]),
+}
+template <int N>
+MDE_DEV void wait_vm_n() {
+}
+
+constexpr int KT = 64;""", 1)]),
     # attn16 (16x16x32 attention): the exponentials replaced by their argument
     "a16_noexp": ("attention.hip", [
         ("pb.v[s][r] = (f16)__builtin_amdgcn_exp2f(sc.v[0][s][r]);\n        pb.v[s][4 + r] = (f16)__builtin_amdgcn_exp2f(sc.v[1][s][r]);",
@@ -156,7 +156,7 @@ VARIANTS = {
          "hin ? ha[k] : hb[k];", 1)]),
     # direct conv: weights never loaded (LDS garbage)
     "conv_now": ("conv.hip", [
-        ("for (int q = wave; q < BINS; q += NW) glds16c(", "for (int q = wave; q < 0; q += NW) glds16c(", 1)]),
+        ("for (int q = wave; q < BINS; q += NW) glds16(", "for (int q = wave; q < 0; q += NW) glds16(", 1)]),
     # direct conv: no patch at all (LDS garbage): weights, MFMA and epilogue only
     "conv_nopatch": ("conv.hip", [
         ("  auto load_patch = [&](int chunk) {\n    const int cbase = chunk * CK;",
