@@ -505,6 +505,56 @@ size_t mde_op_depth_eval_ws_bytes(int batch, int h, int w);
 int mde_op_depth_eval(const float* pred, const float* gt, const unsigned char* mask, int batch, int h, int w,
                       int policy, int pred_is_inverse, int fit_finite_only, float max_depth, double* out, void* ws,
                       size_t ws_bytes, void* stream);
+/* Colour frames (added to ABI 11 without a new version number, as the point cloud and the evaluation were):
+ * the closing lines of the reference drivers (models/depth_pro/onnx2trt.py:156-168,
+ * models/depth_anything_v2/onnx2trt.py:131-150, models/vggt/onnx2trt.py:122-142) and core/viz.py:colorize,
+ * on the device.  map is fp32 [batch][h][w] (the output of mde_op_depth_postprocess / mde_op_dp_postprocess),
+ * out_u8 is uint8 [batch][h][w][3], tightly packed.  lut257x3 is a device uchar[257][3] in R, G, B order:
+ * entries 0..255 are the colour map, entry 256 the colour of a pixel that has no index ("bad").
+ * swap_rb != 0 writes B, G, R (the reference's cvtColor(RGB2BGR)).  range_out may be null; otherwise a
+ * device float[batch][2] that receives the range actually used.  Each image is ranged on its own.  Every
+ * float operation is float32 and rounded separately, division is IEEE; mode 2 is float64.
+ *   mode 0, inverse_auto (the metric drivers: inverse depth clipped to [1/250, 10] for display):
+ *     v   = map_is_inverse ? x : 1.0f / x
+ *     vmn, vmx = min, max of v over the pixels whose v is finite
+ *     c   = (float)(1.0 / 250)
+ *     lo  = vmn > c ? vmn : c          hi = vmx < 10.0f ? vmx : 10.0f
+ *     d   = (vmx > 10.0f && vmn <= c) ? (float)(10.0 - 1.0 / 250 + denom_eps)    sum in double, one rounding
+ *                                     : (hi - lo) + (float)denom_eps             float32
+ *     n   = (v - lo) / d;  t = n * 256.0f
+ *     index: NaN t -> 256 (bad); t < 0 -> 0; t >= 256 -> 255; else (int)t
+ *     range_out = {lo, hi}
+ *     (the two-way d is the reference's arithmetic under NumPy's promotion rules: Python's min / max return
+ *     Python floats when both ends clip, so that one difference is taken in double; denom_eps = 1e-6 is
+ *     the VGGT driver's variant)
+ *   mode 1, minmax_u8 (the relative driver):
+ *     mn, mx over finite x;  q = ((x - mn) / (mx - mn)) * 255.0f
+ *     index: NaN q -> 256; q < 0 (-inf) -> 0; q >= 255 (+inf) -> 255; else (int)q
+ *     range_out = {mn, mx}
+ *   modes 0 and 1 without one finite value: range_out = {NaN, NaN} and every pixel is bad; a constant map
+ *     (with denom_eps == 0) gives 0 / 0 and is bad, as matplotlib draws it
+ *   mode 2, fixed (core/viz.py:colorize, a caller-given axis, "never on its own range"), in float64:
+ *     vmax <= vmin -> vmax = vmin + 1e-6
+ *     t = clamp(((double)x - vmin) / (vmax - vmin), 0, 1);  index = min((int)(t * 256), 255)
+ *     non-finite x (or a NaN t, from an infinite bound) -> 256
+ *     range_out = {(float)vmin, (float)vmax};  map_is_inverse and denom_eps are ignored
+ * Modes 0 and 1 take three kernels: a workgroup owns MDE_DEPTH_COLORIZE_TILE consecutive pixels of one image
+ * and writes that tile's min and max to ws, one workgroup per image finishes lo, hi and d, and the colour
+ * pass looks the table up; mode 2 is the colour pass alone.  Pixels before the first and after the last
+ * 16-byte aligned group of 16 take one more, scalar launch.  No workgroup waits on another's writes and
+ * there are no floating-point atomics: the same bytes on every run.  Bytes past batch * h * w * 3 of out_u8
+ * are not written.  ws: mde_op_depth_colorize_ws_bytes(batch, h, w) bytes of device scratch, 4-byte aligned
+ * (0 is returned for sizes the op refuses); mode 2 reads none.  The kernels are pinned byte for byte to
+ * monocular_depth_estimation_trt_amd/visualize.py:colorize_np.  mde_op_depth_colorize only enqueues on
+ * `stream` (no allocation, no synchronisation, no host read: capturable).  MDE_ERR_ARG, before any device
+ * call: a null map, out_u8 or lut257x3; a non-positive size; a mode outside 0..2; NaN denom_eps; mode 2
+ * with a NaN bound; h * w of 2^31 - 256 or more; batch > 65535; in modes 0 and 1 ws null, ws_bytes too
+ * small or ws not 4-byte aligned; range_out not 4-byte aligned. */
+#define MDE_DEPTH_COLORIZE_TILE 4096
+size_t mde_op_depth_colorize_ws_bytes(int batch, int h, int w);
+int mde_op_depth_colorize(const float* map, int batch, int h, int w, int mode, int map_is_inverse, double denom_eps,
+                          double vmin, double vmax, const unsigned char* lut257x3, int swap_rb,
+                          unsigned char* out_u8, float* range_out, void* ws, size_t ws_bytes, void* stream);
 /* Depth Pro pyramid patches (upstream DepthProEncoder._create_pyramid + _split, reference engine input
  * "input"): fp32 NCHW image [batch][3][size][size] (size = 4 * 384) -> f16 patch-embed rows
  * [nseq * batch * 576][768] ((c, py, px) order), sequence s = patch * batch + image with the 25

@@ -230,6 +230,15 @@ size_t depth_eval_ws_bytes(int B, int h, int w);
 hipError_t launch_depth_eval(const float* pred, const float* gt, const unsigned char* mask, int B, int h, int w,
                              int policy, int pred_is_inverse, int fit_finite_only, float max_depth, double* out,
                              void* ws, hipStream_t st);
+// depth_colorize.hip: fp32 map [B][h][w] -> uint8 picture [B][h][w][3] through a 257-entry colour
+// table (include/mde.h, mde_op_depth_colorize: inverse_auto, minmax_u8 or a fixed axis); range_out
+// float[B][2] optional; ws = depth_colorize_ws_bytes() of 4-byte aligned scratch (modes 0 and 1).
+// Enqueues at most four kernels, nothing else.  No argument checks here: the ABI wrapper in
+// ops_abi.hip holds the only copy of the limits
+size_t depth_colorize_ws_bytes(int B, int h, int w);
+hipError_t launch_depth_colorize(const float* map, int B, int h, int w, int mode, int map_is_inverse, double denom_eps,
+                                 double vmin, double vmax, const unsigned char* lut257x3, int swap_rb,
+                                 unsigned char* out, float* range_out, void* ws, hipStream_t st);
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H,
                              int W, int ph, int pw, int T, int D, hipStream_t st, h16* Xh = nullptr,
                              float* lnst = nullptr, const float* cls_st = nullptr, float* P32 = nullptr);

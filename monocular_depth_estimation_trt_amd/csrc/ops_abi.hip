@@ -186,6 +186,31 @@ int mde_op_depth_eval(const float* pred, const float* gt, const unsigned char* m
          "mde_op_depth_eval");
 }
 
+size_t mde_op_depth_colorize_ws_bytes(int batch, int h, int w) {
+  if (depth_eval_geometry_error(batch, h, w)) return 0;  // the same limits: unsigned pixel index, grid.y
+  return depth_colorize_ws_bytes(batch, h, w);
+}
+
+int mde_op_depth_colorize(const float* map, int batch, int h, int w, int mode, int map_is_inverse, double denom_eps,
+                          double vmin, double vmax, const unsigned char* lut257x3, int swap_rb, unsigned char* out_u8,
+                          float* range_out, void* ws, size_t ws_bytes, void* st) {
+  const char* why = (!map || !out_u8 || !lut257x3) ? "null pointer" : depth_eval_geometry_error(batch, h, w);
+  if (!why && (mode < 0 || mode > 2)) why = "mode must be 0 (inverse_auto), 1 (minmax_u8) or 2 (fixed)";
+  if (!why && !(denom_eps == denom_eps)) why = "denom_eps is NaN";
+  if (!why && mode == 2 && !(vmin == vmin && vmax == vmax)) why = "vmin or vmax is NaN";
+  if (!why && mode != 2) {
+    if (!ws || ws_bytes < depth_colorize_ws_bytes(batch, h, w))
+      why = "modes 0 and 1 need ws of mde_op_depth_colorize_ws_bytes()";
+    else if (reinterpret_cast<uintptr_t>(ws) & 3)
+      why = "ws must be 4-byte aligned";
+  }
+  if (!why && range_out && (reinterpret_cast<uintptr_t>(range_out) & 3)) why = "range_out must be 4-byte aligned";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_depth_colorize: ") + why);
+  OP_RET(launch_depth_colorize(map, batch, h, w, mode, map_is_inverse != 0, denom_eps, vmin, vmax, lut257x3,
+                               swap_rb != 0, out_u8, range_out, ws, (hipStream_t)st),
+         "mde_op_depth_colorize");
+}
+
 int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
   if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
   DpPyramid pyr;

@@ -14,6 +14,7 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
         [--ply out.ply --f-px F [--ply-step N]]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
+        [--color out.png [--color-range VMIN VMAX]]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed -- taken through the
@@ -50,6 +51,15 @@ the engine's output binding.  The alignment comes from the model's spec.json:
 line is printed and the result written as JSON (`--gt-out`, default
 <out-dir>/<model>_gt.json); `--max-depth` drops ground truth beyond the
 sensor's range.
+
+`--color PATH` is the reference drivers' closing picture (onnx2trt.py:131-151):
+the map, turbo-coloured, BGR, drawn on the device (visualize.DeviceColorize)
+while the map is still there -- 3 bytes per pixel come back.  The recipe comes
+from the spec's `depth_scale`: metric -> inverse depth clipped to [1/250, 10],
+relative -> the map's own min..max in 256 steps.  `--color-range VMIN VMAX`
+draws depth on that fixed axis instead (the reference's core/viz.py:colorize).
+One `[MDET] color : ...` line is printed; the picture is an image file when
+Pillow is installed, else a .npy holding the uint8 [H,W,3] BGR array.
 """
 
 import argparse
@@ -58,7 +68,7 @@ import time
 
 import numpy as np
 
-from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, weights
+from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, visualize, weights
 from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
@@ -101,6 +111,7 @@ def build_parser(model="depth_anything_v2", mc=None):
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
     ap.add_argument("--f-px", type=float, default=None, help="with --ply: focal length in pixels at the source size")
     evaluate.add_gt_arguments(ap)
+    visualize.add_color_arguments(ap)
     return ap
 
 
@@ -158,6 +169,7 @@ def main(argv=None, model="depth_anything_v2"):
     if a.ply:
         _check_ply(a, mc)
     gt_policy = evaluate.check_gt_arguments(a, model_spec, device_map=not a.host_postprocess)
+    visualize.check_color_arguments(a, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
     if a.src_hw is None:
         a.src_hw = list(img.shape[:2]) if img is not None else [2268, 3024]
@@ -204,6 +216,8 @@ def main(argv=None, model="depth_anything_v2"):
             depth = outs[0].reshape(output_shape)[0].copy()
             if gt_policy:  # no post-process: the engine's output binding is the map
                 evaluate.driver_score(a, model, gt_policy, gt_maps, outputs[0].device, gt_hw, stream)
+            if a.color:
+                visualize.driver_color(a, model_spec, outputs[0].device, gt_hw, stream)
         elif a.host_postprocess:
             depth = postprocess(outs[0].reshape(output_shape), a.src_hw)
         else:  # the engine's output is still in outputs[0].device
@@ -216,6 +230,8 @@ def main(argv=None, model="depth_anything_v2"):
                           f"{a.ply_step} -> {a.ply} : {ms:0.3f} ms, {n} points")
                 if gt_policy:
                     evaluate.driver_score(a, model, gt_policy, gt_maps, pp.mem.device, gt_hw, stream)
+                if a.color:
+                    visualize.driver_color(a, model_spec, pp.mem.device, gt_hw, stream)
         bench.record(model, samples, warmup=a.warmup, precision="fp16", profile="bench",
                      variant="u8" if u8 else "single",
                      input_h=input_h, input_w=input_w, engine_path=a.engine, outputs={"depth": depth},

@@ -13,6 +13,7 @@
         [--input x.npy] [--src-hw H W] [--f-px F] [--host-preprocess] [--host-postprocess]
         [--ply out.ply] [--ply-step N]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
+        [--color out.png [--color-range VMIN VMAX]]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed.  It is normalised and
@@ -44,6 +45,15 @@ device post-process left there, with the alignment the spec's `depth_scale`
 earns (metric: none).  One `[MDET] gt : ...` line is printed and the result
 written as JSON (`--gt-out`, default <out-dir>/depth_pro_gt.json);
 `--max-depth` drops ground truth beyond the sensor's range.
+
+`--color PATH` is the reference driver's closing picture (onnx2trt.py:156-176):
+inverse depth clipped to [1/250, 10], turbo-coloured, BGR, drawn on the device
+(visualize.DeviceColorize) while the map is still there -- 3 bytes per pixel
+come back.  `--color-range VMIN VMAX` draws depth on that fixed axis in metres
+instead (the reference's core/viz.py:colorize).  One `[MDET] color : ...` line
+is printed; the picture is an image file when Pillow is installed, else a .npy
+holding the uint8 [H,W,3] BGR array.  models/depth_pro/stream.py does the same
+for a frame sequence.
 """
 
 import argparse
@@ -53,7 +63,7 @@ import time
 
 import numpy as np
 
-from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, weights_depth_pro
+from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, visualize, weights_depth_pro
 from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
                                                                stream_synchronize)
 from monocular_depth_estimation_trt_amd.pointcloud import device_ply
@@ -94,6 +104,7 @@ def build_parser(model="depth_pro", size=None):
                     help="write the point cloud (binary PLY; colours from --image) of the metric depth")
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
     evaluate.add_gt_arguments(ap)
+    visualize.add_color_arguments(ap)
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out-dir", default=os.path.join(os.getcwd(), "reports", "bench"))
@@ -141,13 +152,14 @@ def _device_preprocess(img, size, mem, stream):
         ev.free()
 
 
-def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None):
+def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None, color=None):
     """DepthProDevicePostprocess on the output bindings in place, timed with
     hipEvents (kernel + D2H of the depth map and the focal length); `ply` =
     (path, step, photo or None): then the point cloud of the map, while it is
     still on the device, with the focal length the post-process used (the
     fourth result, pointcloud.device_ply's; else None); `score`: called with
-    the map's device pointer while it is still there (--gt)."""
+    the map's device pointer while it is still there (--gt); `color`: likewise
+    (--color)."""
     if f_px is None and len(outputs) < 2:
         raise SystemExit("this engine has no fov_deg output: pass --f-px")
     ev = _Events(stream)
@@ -166,6 +178,8 @@ def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=Non
                                    d_f_px=pp.f_px.device, f_px=f_px, z_lo=1e-4, z_hi=1e4)
             if score:
                 score(pp.mem.device)
+            if color:
+                color(pp.mem.device)
             return depth, f, ms, cloud
     finally:
         ev.free()
@@ -187,6 +201,7 @@ def main(argv=None, model="depth_pro"):
     if a.ply and a.ply_step < 1:
         raise SystemExit("--ply-step must be positive")
     gt_policy = evaluate.check_gt_arguments(a, s, device_map=not a.host_postprocess)
+    visualize.check_color_arguments(a, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
     if img is not None and not a.host_preprocess:
         x = None  # filled on the device, below
@@ -230,8 +245,10 @@ def main(argv=None, model="depth_pro"):
         else:  # the engine's outputs are still in outputs[*].device
             score = (lambda d_map: evaluate.driver_score(a, model, gt_policy, gt_maps, d_map, src_hw, stream)) if gt_policy \
                 else None
+            color = (lambda d_map: visualize.driver_color(a, s, d_map, src_hw, stream)) if a.color else None
             depth, f_px, ms, cloud = _device_postprocess(outputs, size, src_hw, a.f_px, stream,
-                                                         ply=(a.ply, a.ply_step, img) if a.ply else None, score=score)
+                                                         ply=(a.ply, a.ply_step, img) if a.ply else None, score=score,
+                                                         color=color)
             print(f"[MDET] postprocess (device, kernel + D2H, hipEvents) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{ms:0.3f} ms")
             if cloud:
