@@ -555,6 +555,61 @@ size_t mde_op_depth_colorize_ws_bytes(int batch, int h, int w);
 int mde_op_depth_colorize(const float* map, int batch, int h, int w, int mode, int map_is_inverse, double denom_eps,
                           double vmin, double vmax, const unsigned char* lut257x3, int swap_rb,
                           unsigned char* out_u8, float* range_out, void* ws, size_t ws_bytes, void* stream);
+/* VGGT photo path (added to ABI 11 without a new version number, as the three additions before it): the two
+ * ends of reference models/vggt/onnx2trt.py (:32-53, :121-146) around the engine, over core/preprocess.py:
+ * resize_square_pad -- cvtColor(BGR2RGB), copyMakeBorder(BORDER_CONSTANT, white) to a square, one
+ * cv2.resize(INTER_CUBIC) on uint8, /255 in float32 -- and the crop of the depth map to the content box.
+ * mde_op_resize_cubic_u8 is a restatement of OpenCV's published scalar fixed-point INTER_CUBIC for 8-bit,
+ * 3-channel images; parity with cv2 itself is not pinned in this repository ("VGGT photo path"),
+ * the kernel is pinned bit for bit to monocular_depth_estimation_trt_amd/preprocess.py:resize_cubic_u8.
+ * One more caveat than for the linear resize: vectorised builds of OpenCV evaluate the VERTICAL pass in
+ * float32 (beta / 2^22 multiply-adds, then round) instead of the integer form below, and can differ from it
+ * by one level on pixels whose exact sum sits at a rounding boundary.  The contract is the scalar integer form:
+ *   virtual source: ph = pad_top + sh + pad_bottom rows by pw = pad_left + sw + pad_right columns; pixel
+ *     (y, x) of it is the photo's pixel (y - pad_top, x - pad_left) where that lies inside the photo and the
+ *     pad colour everywhere else.  No padded copy is made.  All four pads zero: a plain cubic resize.
+ *   per axis (dst outputs from src = pw or ph inputs), the same on both axes; unlike the linear kernel no
+ *   fraction is zeroed at a border
+ *     scale = 1.0 / ((double)dst / (double)src)        float64; NOT src / dst
+ *     f     = (float)((d + 0.5) * scale - 0.5)         float64, rounded once to float32
+ *     s     = floor(f);  x = f - s                     float32
+ *     taps  = s - 1, s, s + 1, s + 2, each clamped to [0, src - 1] of the VIRTUAL image
+ *   coefficients, float32, every operation rounded separately in exactly this order, never fused;
+ *   A = -0.75f (the constants 5A, 8A, 4A, A + 2, A + 3 are exact)
+ *     x1 = x + 1
+ *     c0 = ((A*x1 - 5*A)*x1 + 8*A)*x1 - 4*A
+ *     c1 = (((A + 2)*x - (A + 3))*x)*x + 1
+ *     g  = 1 - x
+ *     c2 = (((A + 2)*g - (A + 3))*g)*g + 1
+ *     c3 = ((1 - c0) - c1) - c2
+ *     k_i = rint(c_i * 2048.f)      half to even; the four need not sum to 2048 (2047..2049 occur)
+ *   horizontal pass, exact integers, no shift
+ *     H = sum_i S[tap_i] * a_i
+ *   vertical pass
+ *     V = sum_j H_j * b_j;  out = clamp((V + (1 << 21)) >> 22, 0, 255)         arithmetic shift
+ *     (sum |c_i| <= 1.375, reached at x = 0.5, so |V| + 2^21 <= 255 * 2818^2 + 2^21 < 2^31: int32 holds it)
+ * src is [batch][sh][pitch] bytes with the rules of mde_op_resize_u8 (3 interleaved channels per pixel,
+ * pitch >= 3 * sw, bytes of a row past 3 * sw are never read, swap_rb != 0 writes source channel 2 - c to
+ * output channel c).  pad_c0, pad_c1, pad_c2 are the pad colour, host ints 0..255 in OUTPUT channel order
+ * (the reference pads after its BGR -> RGB).  mde_op_resize_cubic_u8 writes uint8 NHWC [batch][oh][ow][3];
+ * mde_op_resize_cubic_u8_norm writes float32 NCHW [batch][3][oh][ow] = lut3x256[c][value] (the engine's
+ * "images" binding [1][S][3][oh][ow] with batch = S), lut3x256 a device float[3][256] indexed by output channel
+ * and resized pixel value (preprocess.py:vggt_lut: float32(u) / 255).
+ * mde_op_crop_f32 copies the window rows [y0, y0 + ch), columns [x0, x0 + cw) of each fp32 map [batch][h][w]
+ * to dst [batch][ch][cw], tightly packed (the reference's depth[round(y1):round(y2), round(x1):round(x2)]).
+ * Each of the three only enqueues one kernel on `stream` (no allocation, no synchronisation: capturable);
+ * nothing is written outside the destination.  MDE_ERR_ARG, before any device call: a null pointer; a
+ * non-positive size; pitch < 3 * sw; a negative pad; a pad colour outside 0..255; a source, virtual or
+ * destination plane of 2^31 - 256 elements or more; batch > 65535; a crop window not inside [0, h) x [0, w). */
+int mde_op_resize_cubic_u8(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                           int pad_top, int pad_bottom, int pad_left, int pad_right, int pad_c0, int pad_c1,
+                           int pad_c2, unsigned char* dst_u8, int oh, int ow, void* stream);
+int mde_op_resize_cubic_u8_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                                int pad_top, int pad_bottom, int pad_left, int pad_right, int pad_c0, int pad_c1,
+                                int pad_c2, const float* lut3x256, float* dst_f32_nchw, int oh, int ow,
+                                void* stream);
+int mde_op_crop_f32(const float* src, int batch, int h, int w, int y0, int x0, int ch, int cw, float* dst,
+                    void* stream);
 /* Depth Pro pyramid patches (upstream DepthProEncoder._create_pyramid + _split, reference engine input
  * "input"): fp32 NCHW image [batch][3][size][size] (size = 4 * 384) -> f16 patch-embed rows
  * [nseq * batch * 576][768] ((c, py, px) order), sequence s = patch * batch + image with the 25

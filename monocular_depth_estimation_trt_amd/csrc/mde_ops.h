@@ -239,6 +239,17 @@ size_t depth_colorize_ws_bytes(int B, int h, int w);
 hipError_t launch_depth_colorize(const float* map, int B, int h, int w, int mode, int map_is_inverse, double denom_eps,
                                  double vmin, double vmax, const unsigned char* lut257x3, int swap_rb,
                                  unsigned char* out, float* range_out, void* ws, hipStream_t st);
+// preprocess_cubic.hip: cv2's uint8 INTER_CUBIC of [B][sh][pitch] 3-channel rows seen through a virtual
+// constant border of pad_* pixels (include/mde.h, mde_op_resize_cubic_u8; pad_rgb in output channel
+// order); lut == nullptr: dst uint8 NHWC [B][oh][ow][3]; else dst float NCHW [B][3][oh][ow] =
+// lut[c][value] (lut float[3][256]).  launch_crop_f32: the window [y0, y0 + ch) x [x0, x0 + cw) of fp32
+// maps [B][h][w] -> [B][ch][cw].  One kernel each.  No argument checks here: the ABI wrappers in
+// ops_abi.hip hold the only copy of the limits
+hipError_t launch_resize_cubic_u8(const unsigned char* src, int B, int sh, int sw, int pitch, int swap_rb,
+                                  int pad_top, int pad_bottom, int pad_left, int pad_right, const int pad_rgb[3],
+                                  const float* lut, void* dst, int oh, int ow, hipStream_t st);
+hipError_t launch_crop_f32(const float* src, int B, int h, int w, int y0, int x0, int ch, int cw, float* dst,
+                           hipStream_t st);
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H,
                              int W, int ph, int pw, int T, int D, hipStream_t st, h16* Xh = nullptr,
                              float* lnst = nullptr, const float* cls_st = nullptr, float* P32 = nullptr);

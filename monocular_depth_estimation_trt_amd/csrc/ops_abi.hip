@@ -211,6 +211,64 @@ int mde_op_depth_colorize(const float* map, int batch, int h, int w, int mode, i
          "mde_op_depth_colorize");
 }
 
+namespace {
+// the cubic resize indexes the source, the virtual (padded) and the destination plane with an int
+// and puts the batch on grid.y
+const char* resize_cubic_arg_error(const void* src, const void* dst, int batch, int sh, int sw, int pitch,
+                                   int pad_top, int pad_bottom, int pad_left, int pad_right, int c0, int c1, int c2,
+                                   int oh, int ow) {
+  if (!src || !dst) return "null pointer";
+  if (batch < 1 || sh < 1 || sw < 1 || oh < 1 || ow < 1) return "batch and sizes must be positive";
+  if (pitch < 3 * (long long)sw) return "pitch < 3 * sw";
+  if (pad_top < 0 || pad_bottom < 0 || pad_left < 0 || pad_right < 0) return "negative pad";
+  if ((c0 | c1 | c2) < 0 || c0 > 255 || c1 > 255 || c2 > 255) return "pad colour outside 0..255";
+  const long long lim = 0x7fffffffLL - 256;
+  const long long ph = (long long)pad_top + sh + pad_bottom, pw = (long long)pad_left + sw + pad_right;
+  // ph and pw are tested alone first: below 2^31 each, their product cannot overflow 64 bits
+  if ((long long)sh * sw >= lim || ph >= lim || pw >= lim || ph * pw >= lim || (long long)oh * ow >= lim)
+    return "a plane of 2^31 - 256 elements or more";
+  if (batch > 65535) return "batch > 65535";
+  return nullptr;
+}
+}  // namespace
+
+int mde_op_resize_cubic_u8(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb, int pad_top,
+                           int pad_bottom, int pad_left, int pad_right, int pad_c0, int pad_c1, int pad_c2,
+                           unsigned char* dst_u8, int oh, int ow, void* st) {
+  if (const char* why = resize_cubic_arg_error(src, dst_u8, batch, sh, sw, pitch, pad_top, pad_bottom, pad_left,
+                                               pad_right, pad_c0, pad_c1, pad_c2, oh, ow))
+    return fail(MDE_ERR_ARG, std::string("mde_op_resize_cubic_u8: ") + why);
+  const int pad_rgb[3] = {pad_c0, pad_c1, pad_c2};
+  OP_RET(launch_resize_cubic_u8(src, batch, sh, sw, pitch, swap_rb, pad_top, pad_bottom, pad_left, pad_right, pad_rgb,
+                                nullptr, dst_u8, oh, ow, (hipStream_t)st),
+         "mde_op_resize_cubic_u8");
+}
+
+int mde_op_resize_cubic_u8_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                                int pad_top, int pad_bottom, int pad_left, int pad_right, int pad_c0, int pad_c1,
+                                int pad_c2, const float* lut3x256, float* dst_f32_nchw, int oh, int ow, void* st) {
+  const char* why = resize_cubic_arg_error(src, dst_f32_nchw, batch, sh, sw, pitch, pad_top, pad_bottom, pad_left,
+                                           pad_right, pad_c0, pad_c1, pad_c2, oh, ow);
+  if (!why && !lut3x256) why = "null pointer";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_resize_cubic_u8_norm: ") + why);
+  const int pad_rgb[3] = {pad_c0, pad_c1, pad_c2};
+  OP_RET(launch_resize_cubic_u8(src, batch, sh, sw, pitch, swap_rb, pad_top, pad_bottom, pad_left, pad_right, pad_rgb,
+                                lut3x256, dst_f32_nchw, oh, ow, (hipStream_t)st),
+         "mde_op_resize_cubic_u8_norm");
+}
+
+int mde_op_crop_f32(const float* src, int batch, int h, int w, int y0, int x0, int ch, int cw, float* dst, void* st) {
+  const char* why = nullptr;
+  if (!src || !dst) why = "null pointer";
+  else if (batch < 1 || h < 1 || w < 1 || ch < 1 || cw < 1) why = "batch and sizes must be positive";
+  else if (y0 < 0 || x0 < 0 || (long long)y0 + ch > h || (long long)x0 + cw > w)
+    why = "the window is not inside [0, h) x [0, w)";
+  else if ((long long)h * w >= 0x7fffffffLL - 256) why = "a plane of 2^31 - 256 elements or more";
+  else if (batch > 65535) why = "batch > 65535";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_crop_f32: ") + why);
+  OP_RET(launch_crop_f32(src, batch, h, w, y0, x0, ch, cw, dst, (hipStream_t)st), "mde_op_crop_f32");
+}
+
 int mde_op_dp_pyramid_patches(const float* img, int batch, int size, void* patches, void* st) {
   if (!img || !patches || batch < 1 || size != 1536) return fail(MDE_ERR_ARG, "mde_op_dp_pyramid_patches: bad argument");
   DpPyramid pyr;

@@ -13,7 +13,8 @@ to `resize_linear_u8`, and `resize_linear_u8` stays within one level of exact
 bilinear interpolation.
 
 Depth Pro's pre-process is another function (normalise, then torch's float32
-bilinear) and has its own section at the end of this module.
+bilinear) and has its own section further down; VGGT's (square pad with
+white, one cv2 INTER_CUBIC on uint8, /255) is the last section.
 """
 
 from __future__ import annotations
@@ -337,6 +338,177 @@ class DepthProPreprocess(_FramePreprocess):
                       self.dst[0], self.dst[1], stream)
 
 
+# ---- VGGT --------------------------------------------------------------------
+# Reference models/vggt/onnx2trt.py:32-53 over core/preprocess.py:
+# resize_square_pad and _builders().vggt: BGR->RGB, pad to a square with white
+# at source resolution, ONE cv2.resize(INTER_CUBIC) on uint8 to size^2, /255 in
+# float32, rank 5.  The contract is spelled out in include/mde.h at
+# mde_op_resize_cubic_u8; resize_cubic_u8 restates OpenCV's published scalar
+# fixed-point algorithm in numpy integers, and the kernel
+# (csrc/preprocess_cubic.hip) is held to it bit for bit.  As for the linear
+# resize, parity with cv2 itself is not pinned here (cv2 is not a dependency).
+# One more caveat for cubic: vectorised builds of OpenCV evaluate the vertical
+# pass in float32 (beta / 2^22 multiply-adds, then round) instead of the integer
+# form, and can differ from it by one level on pixels whose exact sum sits at a
+# rounding boundary.  The contract is the scalar integer form.  What is pinned:
+# the kernel is bit-identical to resize_cubic_u8, and resize_cubic_u8 stays
+# within the bound derived in DESIGN.md ("VGGT photo path") of exact bicubic
+# interpolation.
+
+CUBIC_A = np.float32(-0.75)  # cv2's interpolateCubic
+VGGT_PAD = (255, 255, 255)   # core/preprocess.py:_builders().vggt pad_value
+
+
+def _axis_cubic(dst: int, src: int):
+    """Per output index of one axis: (taps int32 [4][dst], clamped to
+    [0, src - 1], weights int32 [4][dst]); float32 with one rounding per
+    operation, in the contract's order."""
+    f32 = np.float32
+    scale = 1.0 / (float(dst) / float(src))  # float64; not src / dst
+    pos = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    base = np.floor(pos)
+    x = pos - base  # float32
+    A, one = CUBIC_A, f32(1)
+    x1 = x + one
+    c0 = ((A * x1 - f32(5) * A) * x1 + f32(8) * A) * x1 - f32(4) * A
+    c1 = (((A + f32(2)) * x - (A + f32(3))) * x) * x + one
+    g = one - x
+    c2 = (((A + f32(2)) * g - (A + f32(3))) * g) * g + one
+    c3 = ((one - c0) - c1) - c2
+    c = np.stack([c0, c1, c2, c3])
+    assert c.dtype == np.float32
+    k = np.rint(c * f32(1 << COEF_BITS)).astype(np.int32)
+    taps = np.clip(base.astype(np.int32)[None] + np.arange(-1, 3, dtype=np.int32)[:, None], 0, src - 1)
+    return taps, k
+
+
+def resize_cubic_u8(img_hwc_u8: np.ndarray, oh: int, ow: int, pad=(0, 0, 0, 0), pad_value=(0, 0, 0)) -> np.ndarray:
+    """`cv2.resize(cv2.copyMakeBorder(img, *pad, cv2.BORDER_CONSTANT, value=
+    pad_value), (ow, oh), interpolation=cv2.INTER_CUBIC)` for a uint8
+    [H, W, 3] image, in numpy integer arithmetic: whole-image gathers through
+    per-axis tables, the horizontal pass first (exact integers, no shift), then
+    the vertical pass with cv2's one rounding shift and the clamp to 0..255.
+    pad = (top, bottom, left, right); pad_value is in the image's own channel
+    order.  The border is materialised here, on the host, only."""
+    img = np.asarray(img_hwc_u8)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"resize_cubic_u8 wants a uint8 [H, W, 3] image, got {img.dtype} {img.shape}")
+    oh, ow = int(oh), int(ow)
+    top, bottom, left, right = (int(p) for p in pad)
+    value = np.asarray(pad_value)
+    if oh < 1 or ow < 1 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("resize_cubic_u8: sizes must be positive")
+    if min(top, bottom, left, right) < 0:
+        raise ValueError(f"resize_cubic_u8: negative pad {pad}")
+    if value.shape != (3,) or (value < 0).any() or (value > 255).any():
+        raise ValueError(f"resize_cubic_u8: pad_value must be three values in 0..255, got {pad_value!r}")
+    sh, sw = img.shape[:2]
+    padded = np.empty((top + sh + bottom, left + sw + right, 3), np.uint8)
+    padded[:] = value.astype(np.uint8)
+    padded[top:top + sh, left:left + sw] = img
+    tx, a = _axis_cubic(ow, padded.shape[1])
+    ty, b = _axis_cubic(oh, padded.shape[0])
+    # int32 holds every intermediate: sum |k| <= 2818 per axis, 255 * 2818^2 + 2^21 < 2^31
+    rows = sum(padded[:, tx[i]].astype(np.int32) * a[i][None, :, None] for i in range(4))
+    v = sum(rows[ty[j]] * b[j][:, None, None] for j in range(4))
+    assert v.dtype == np.int32
+    return np.clip((v + (1 << 21)) >> 22, 0, 255).astype(np.uint8)
+
+
+def square_pad_geometry(h: int, w: int, dst: int):
+    """((top, bottom, left, right), (x1, y1, x2, y2)) of the reference's
+    resize_square_pad(symmetric=True): the same count on both sides, so an odd
+    difference leaves the padded frame one short of square (768 x 1025 is
+    padded to 1024 x 1025 and the two axes get different scales); the float
+    box, on the dst x dst grid, uses dst / max_dim all the same -- these four
+    floats are what the crop rounds."""
+    h, w, dst = int(h), int(w), int(dst)
+    if h < 1 or w < 1 or dst < 1:
+        raise ValueError("square_pad_geometry: sizes must be positive")
+    max_dim = max(h, w)
+    left = (max_dim - w) // 2
+    top = (max_dim - h) // 2
+    scale = dst / max_dim
+    return (top, top, left, left), (left * scale, top * scale, (left + w) * scale, (top + h) * scale)
+
+
+def box_window(box):
+    """(y0, x0, ch, cw) of the reference's depth[int(round(y1)):int(round(y2)),
+    int(round(x1)):int(round(x2))]."""
+    x1, y1, x2, y2 = (int(round(v)) for v in box)
+    return y1, x1, y2 - y1, x2 - x1
+
+
+def vggt_lut() -> np.ndarray:
+    """float32 [3][256]: pixel value u after the reference's scale,
+    float32(u) / 255 in float32, the same for every channel."""
+    u = np.arange(256, dtype=np.float32) / np.float32(255)
+    return np.ascontiguousarray(np.broadcast_to(u, (3, 256)))
+
+
+def _vggt_frames(frames_bgr) -> np.ndarray:
+    fr = np.asarray(frames_bgr)
+    if fr.ndim == 3:
+        fr = fr[None]
+    if fr.dtype != np.uint8 or fr.ndim != 4 or fr.shape[3] != 3 or fr.shape[0] < 1:
+        raise ValueError(f"VGGT wants uint8 BGR frames [S, H, W, 3] of one size, got {fr.dtype} {fr.shape}")
+    return fr
+
+
+def preprocess_vggt_host(frames_bgr, size: int):
+    """BGR uint8 frames [S, H, W, 3] (or one [H, W, 3]) -> (float32
+    [1, S, 3, size, size] blob in [0, 1], box (x1, y1, x2, y2)):
+    `core/preprocess.py:preprocess_for(frame, 'vggt', (size, size))` per frame
+    on the host."""
+    fr = _vggt_frames(frames_bgr)
+    size = int(size)
+    pad, box = square_pad_geometry(fr.shape[1], fr.shape[2], size)
+    lut = vggt_lut()[0]
+    out = [lut[resize_cubic_u8(f[:, :, ::-1], size, size, pad, VGGT_PAD)].transpose(2, 0, 1) for f in fr]
+    return np.ascontiguousarray(np.stack(out)[None]), box
+
+
+def resize_cubic_u8_device(d_src: int, batch: int, sh: int, sw: int, pitch: int, swap_rb: bool, pad, pad_value,
+                           d_dst: int, oh: int, ow: int, stream: int = 0, d_lut: int = 0) -> None:
+    """Device pointers in/out, enqueued on `stream`: uint8 NHWC out, or with
+    `d_lut` (device float[3][256]) float32 NCHW out.  pad = (top, bottom, left,
+    right); pad_value in output channel order."""
+    head = (C.c_void_p(int(d_src)), int(batch), int(sh), int(sw), int(pitch), int(bool(swap_rb)),
+            *(int(p) for p in pad), *(int(v) for v in pad_value))
+    tail = (C.c_void_p(int(d_dst)), int(oh), int(ow), C.c_void_p(int(stream or 0)))
+    if d_lut:
+        _lib.call("mde_op_resize_cubic_u8_norm", *head, C.c_void_p(int(d_lut)), *tail)
+    else:
+        _lib.call("mde_op_resize_cubic_u8", *head, *tail)
+
+
+def crop_f32(d_src: int, batch: int, h: int, w: int, y0: int, x0: int, ch: int, cw: int, d_dst: int,
+             stream: int = 0) -> None:
+    """Device pointers in/out, enqueued on `stream`: rows [y0, y0 + ch), columns
+    [x0, x0 + cw) of float32 maps [batch][h][w] -> [batch][ch][cw]."""
+    _lib.call("mde_op_crop_f32", C.c_void_p(int(d_src)), int(batch), int(h), int(w), int(y0), int(x0), int(ch),
+              int(cw), C.c_void_p(int(d_dst)), C.c_void_p(int(stream or 0)))
+
+
+class VggtPreprocess(_FramePreprocess):
+    """DevicePreprocess's counterpart for VGGT: owns the S source frames of one
+    size (pinned host + device) and the device LUT float[3][256]; run /
+    run_device / fill_binding write the engine's "images" binding, float32
+    [1][frames][3][size][size], under the same stream-order rules.  `.pad` is
+    the virtual border (top, bottom, left, right), `.box` the content box
+    (x1, y1, x2, y2) on the size x size grid that the crop rounds."""
+
+    def __init__(self, src_h: int, src_w: int, size: int, frames: int = 1):
+        self.pad, self.box = square_pad_geometry(src_h, src_w, size)
+        super().__init__((src_h, src_w), (size, size), frames, "float32_nchw", 4, vggt_lut())
+
+    def _enqueue(self, d_src, pitch, swap_rb, d_dst, stream):
+        resize_cubic_u8_device(d_src, self.batch, self.src[0], self.src[1], pitch, swap_rb, self.pad, VGGT_PAD, d_dst,
+                               self.dst[0], self.dst[1], stream, self.lut.device)
+
+
 __all__ = ["resize_linear_u8", "normalize_lut", "preprocess_host", "load_image_bgr", "resize_u8",
            "DevicePreprocess", "check_second_stage", "depth_pro_lut", "resize_bilinear_f32",
-           "preprocess_depth_pro_host", "dp_preprocess", "DepthProPreprocess"]
+           "preprocess_depth_pro_host", "dp_preprocess", "DepthProPreprocess", "resize_cubic_u8",
+           "square_pad_geometry", "box_window", "vggt_lut", "preprocess_vggt_host", "resize_cubic_u8_device",
+           "crop_f32", "VggtPreprocess"]

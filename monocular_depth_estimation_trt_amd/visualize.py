@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib, colormaps
 from .common_runtime import HostDeviceMem, stream_synchronize
+from .preprocess import resize_u8
 
 MODES = ("inverse_auto", "minmax_u8", "fixed")
 TILE = 4096              # MDE_DEPTH_COLORIZE_TILE
@@ -263,26 +264,42 @@ def save_image(path: str, bgr: np.ndarray) -> str:
     return path
 
 
-def device_color(d_map: int, h: int, w: int, stream: int, mode, **kw):
+def device_color(d_map: int, h: int, w: int, stream: int, mode, resize_hw=None, **kw):
     """What the model drivers' --color does: DeviceColorize on one device map
     [h][w] at `d_map`.  Returns (ms of the kernels + the D2H of the picture
-    between two hipEvents on `stream`, picture uint8 [h, w, 3], (lo, hi))."""
+    between two hipEvents on `stream`, picture uint8 [h, w, 3], (lo, hi)).
+    `resize_hw` = (H, W): the picture is resized to that size on the device
+    (mde_op_resize_u8, cv2's INTER_LINEAR; the VGGT driver's closing resize to
+    the photo's size) and only the resized one, [H, W, 3], is downloaded."""
     s = C.c_void_p(int(stream or 0))
     ev = [C.c_void_p(), C.c_void_p()]
+    big = None
     try:
         for e in ev:
             _lib.call("mde_rt_event_create", C.byref(e))
         with DeviceColorize(1, h, w) as dc:
+            if resize_hw is not None:
+                H, W = int(resize_hw[0]), int(resize_hw[1])
+                big = HostDeviceMem(H * W * 3, np.uint8)
             _lib.call("mde_rt_event_record", ev[0], s)
             dc.enqueue(d_map, stream, mode, **kw)
-            dc.download(stream)
+            if big is None:
+                dc.download(stream)
+            else:
+                resize_u8(dc.out.device, 1, h, w, 3 * w, False, big.device, H, W, stream)
+                for m in (big, dc.rng):
+                    _lib.call("mde_rt_memcpy_dtoh_async", m.host.ctypes.data_as(C.c_void_p), C.c_void_p(m.device),
+                              m.nbytes, s)
             _lib.call("mde_rt_event_record", ev[1], s)
             stream_synchronize(stream)
             ms = C.c_float()
             _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
             lo, hi = dc.range()[0]
-            return float(ms.value), dc.result()[0].copy(), (float(lo), float(hi))
+            pic = dc.result()[0].copy() if big is None else big.host.reshape(H, W, 3).copy()
+            return float(ms.value), pic, (float(lo), float(hi))
     finally:
+        if big is not None:
+            big.free()
         for e in ev:
             if e:
                 _lib.call("mde_rt_event_destroy", e)
@@ -318,11 +335,16 @@ def color_kwargs(a, model_spec: dict) -> dict:
     return {"mode": mode_for(model_spec)}
 
 
-def driver_color(a, model_spec: dict, d_map: int, hw, stream: int) -> np.ndarray:
+def driver_color(a, model_spec: dict, d_map: int, hw, stream: int, resize_hw=None,
+                 denom_eps: float = 0.0) -> np.ndarray:
     """The drivers' --color: colour the device map [hw] at `d_map`, print the
-    `[MDET] color : ...` line and write the picture."""
+    `[MDET] color : ...` line and write the picture.  `resize_hw`: resize it to
+    that size on the device first (device_color); `denom_eps`: the epsilon of
+    the inverse_auto recipe's denominator (the VGGT driver's 1e-6)."""
     kw = color_kwargs(a, model_spec)
-    ms, bgr, (lo, hi) = device_color(d_map, hw[0], hw[1], stream, **kw)
+    if kw["mode"] == "inverse_auto":
+        kw["denom_eps"] = denom_eps
+    ms, bgr, (lo, hi) = device_color(d_map, hw[0], hw[1], stream, resize_hw=resize_hw, **kw)
     path = save_image(a.color, bgr)
     print(f"[MDET] color : mode {kw['mode']} range {lo:0.6g}..{hi:0.6g} (device, kernels + D2H of {bgr.nbytes} "
           f"bytes, hipEvents: {ms:0.3f} ms) -> {path}")
