@@ -555,6 +555,56 @@ size_t mde_op_depth_colorize_ws_bytes(int batch, int h, int w);
 int mde_op_depth_colorize(const float* map, int batch, int h, int w, int mode, int map_is_inverse, double denom_eps,
                           double vmin, double vmax, const unsigned char* lut257x3, int swap_rb,
                           unsigned char* out_u8, float* range_out, void* ws, size_t ws_bytes, void* stream);
+/* Robust display range (added to ABI 11 without a new version number, as the four additions before it): the
+ * reference's core/viz.py:robust_range / display_ranges / qualitative_display and demo.py:distribution, on
+ * the device -- exact percentiles of the valid pixels of fp32 maps [batch][h][w], as np.percentile (method
+ * linear, numpy 2.2) computes them in float64.  out is a device double[rows][8], rows = 1 when pooled, else
+ * batch.  q_percent is a HOST array of nq (1..3) percentages, read before the call returns.
+ *   valid pixel   finite, and > 0 when positive_only; -0 counts as +0
+ *   order         a valid pixel's rank r is its position among the valid pixels of its image, row-major
+ *   subsample     (the reference's v[:: max(1, v.size // 200000)]) stride = max(1, n_valid / sample_cap) in
+ *                 integer division when sample_cap > 0 and n_valid > sample_cap, else 1; a valid pixel is used
+ *                 iff r % stride == 0.  sample_cap = 200000 is the reference's, 0 takes every valid pixel
+ *   sample        per image: the used values widened to float64; pooled: every image's used values together,
+ *                 each image with its own stride; reciprocal: 1.0 / x in float64 of each (1 / 0 = +inf)
+ *   quantile p of the n sorted sample values s, every operation float64 and rounded separately:
+ *                 q = p / 100; vi = (n - 1) * q; prev = floor(vi), next = prev + 1, both n - 1 when vi >= n - 1;
+ *                 g = vi - floor(vi); d = s[next] - s[prev]; g < 0.5 ? s[prev] + d * g : s[next] - d * (1 - g)
+ *   out[row][.]   0 n_valid   1 n_used (the sample's size)   2 min of the sample   3 max of the sample
+ *                 4 quantile 0   5 quantile 1 (0 when nq == 1)   6, 7 the display range {vmin, vmax}
+ *                 nq == 3: slot 3 holds quantile 2 instead of the max -- eight slots cannot hold nine values,
+ *                 and slots 6, 7 are what mde_op_depth_colorize_ranged reads; the max still enters the range
+ *   display range vmin = quantile 0, vmax = quantile nq - 1; if either is not finite or vmax <= vmin: {min,
+ *                 max} of the sample, and if still vmax <= vmin: vmax = vmin + 1.0
+ *   empty sample  slots 2..5 NaN, display range {0.0, 1.0}
+ * Selection is a radix select over four 8-bit digits of an order-preserving 32-bit key (the float's bits,
+ * sign-flipped; under reciprocal a key ordered as 1 / x is), so it is exact: a workgroup owns
+ * MDE_DEPTH_QUANTILES_TILE consecutive pixels of one image, counts digits in LDS and adds them to ws with
+ * integer atomics, whose sums do not depend on the order; there are no floating-point atomics, and the same
+ * 64 bytes per row come out on every run.  ws: mde_op_depth_quantiles_ws_bytes(batch, h, w) bytes of device
+ * scratch, 8-byte aligned (0 is returned for sizes the op refuses; enough for pooled or not); its content on
+ * entry does not matter, the op zeroes what it counts in on `stream`.  The kernels are pinned bit for bit to
+ * monocular_depth_estimation_trt_amd/visualize.py:quantiles_np.  mde_op_depth_quantiles only enqueues on
+ * `stream` (no allocation, no synchronisation, no host read of device memory: capturable).  MDE_ERR_ARG,
+ * before any device call: a null pointer; a non-positive size; nq outside 1..3; a q_percent outside [0, 100]
+ * or NaN; a negative sample_cap; h * w of 2^31 - 256 or more; batch > 65535; pooled with batch * h * w of
+ * 2^31 - 256 or more; ws null, ws_bytes too small; out or ws not 8-byte aligned.
+ * mde_op_depth_colorize_ranged is mode 2 of mde_op_depth_colorize with the axis read from device memory:
+ * image b is drawn on vmin = range_dev[b * range_stride], vmax = range_dev[b * range_stride + 1] (stride 0:
+ * one shared axis; out + 6 of the quantile op with stride 8: its rows).  A pixel is valid when it is finite,
+ * and > 0 when positive_only; y = reciprocal ? 1.0 / (double)x : (double)x; then mode 2's lines on y
+ * (vmax <= vmin -> vmax = vmin + 1e-6, clamp, min((int)(t * 256), 255)); an invalid pixel or a NaN t gets
+ * index 256.  With both flags 0 and the same bounds the picture is mode 2's, byte for byte.  Enqueue only.
+ * MDE_ERR_ARG, before any device call: a null pointer; a non-positive size; a negative range_stride;
+ * range_dev not 8-byte aligned; h * w of 2^31 - 256 or more; batch > 65535. */
+#define MDE_DEPTH_QUANTILES_TILE 4096
+size_t mde_op_depth_quantiles_ws_bytes(int batch, int h, int w);
+int mde_op_depth_quantiles(const float* map, int batch, int h, int w, int positive_only, int reciprocal, int pooled,
+                           int sample_cap, const double* q_percent, int nq, double* out, void* ws, size_t ws_bytes,
+                           void* stream);
+int mde_op_depth_colorize_ranged(const float* map, int batch, int h, int w, int positive_only, int reciprocal,
+                                 const double* range_dev, int range_stride, const unsigned char* lut257x3,
+                                 int swap_rb, unsigned char* out_u8, void* stream);
 /* VGGT photo path (added to ABI 11 without a new version number, as the three additions before it): the two
  * ends of reference models/vggt/onnx2trt.py (:32-53, :121-146) around the engine, over core/preprocess.py:
  * resize_square_pad -- cvtColor(BGR2RGB), copyMakeBorder(BORDER_CONSTANT, white) to a square, one

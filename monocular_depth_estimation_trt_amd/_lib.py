@@ -182,6 +182,11 @@ PROTOTYPES = {
     "mde_op_depth_colorize_ws_bytes": [c_int, c_int, c_int],
     "mde_op_depth_colorize": [c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_double, C.c_double, C.c_double,
                               c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    "mde_op_depth_colorize_ranged": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                     c_void_p, c_void_p],
+    "mde_op_depth_quantiles_ws_bytes": [c_int, c_int, c_int],
+    "mde_op_depth_quantiles": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                               c_void_p, c_size_t, c_void_p],
     "mde_op_resize_cubic_u8": [c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, c_void_p],
     "mde_op_resize_cubic_u8_norm": [c_void_p] + [c_int] * 12 + [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "mde_op_crop_f32": [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p],
@@ -191,7 +196,7 @@ PROTOTYPES = {
 }
 _RESTYPE = {"mde_last_error": c_char_p, "mde_op_attention_ws_bytes": c_size_t,
              "mde_op_point_cloud_ws_bytes": c_size_t, "mde_op_depth_eval_ws_bytes": c_size_t,
-             "mde_op_depth_colorize_ws_bytes": c_size_t}
+             "mde_op_depth_colorize_ws_bytes": c_size_t, "mde_op_depth_quantiles_ws_bytes": c_size_t}
 
 _lib = None
 _lock = threading.Lock()

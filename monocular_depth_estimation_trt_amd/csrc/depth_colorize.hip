@@ -15,6 +15,8 @@
 //   dc_range_finalize   one workgroup per image folds the partials and writes {lo, d} to ws and
 //                       {lo, hi} to range_out
 //   dc_color            the table look-up, below
+// mde_op_depth_colorize_ranged is the colour pass as template mode 3: mode 2's float64 lines on an axis
+// that each image reads from device memory (the rows of mde_op_depth_quantiles), one or two launches.
 // Min and max do not depend on the order they are taken in, no workgroup waits on another's writes and
 // there are no floating-point atomics: the same bytes on every run.
 //
@@ -162,14 +164,30 @@ struct ColorArgs {
   unsigned plane;
   int inverse, swap_rb;
   double vmin, den;          // mode 2: t = (x - vmin) / den
+  const double* range;       // mode 3 (ranged): image b's {vmin, vmax} at range[b * range_stride]
+  int range_stride, positive_only, reciprocal;
 };
 
-// the table index of one pixel; lo, d: this image's (modes 0 and 1)
+// mode 3's axis of image b, with mode 2's rule for an empty one
+__device__ __forceinline__ void ranged_axis(const ColorArgs& a, long long b, double& vmin, double& den) {
+  const double* r = a.range + b * a.range_stride;
+  double vmax = r[1];
+  vmin = r[0];
+  if (vmax <= vmin) vmax = vmin + 1e-6;
+  den = vmax - vmin;
+}
+
+// the table index of one pixel; lo, d: this image's (modes 0 and 1); vmin, den: the axis (modes 2 and 3)
 template <int MODE>
-__device__ __forceinline__ int pixel_index(float x, float lo, float d, const ColorArgs& a) {
-  if (MODE == 2) {
+__device__ __forceinline__ int pixel_index(float x, float lo, float d, double vmin, double den, const ColorArgs& a) {
+  if (MODE >= 2) {
     if (!finite_f(x)) return 256;
-    double t = ((double)x - a.vmin) / a.den;
+    double y = (double)x;
+    if (MODE == 3) {
+      if (a.positive_only && !(x > 0.f)) return 256;
+      if (a.reciprocal) y = 1.0 / y;
+    }
+    double t = (y - vmin) / den;
     if (t != t) return 256;
     t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
     const int i = (int)(t * 256.0);
@@ -213,15 +231,18 @@ dc_color(ColorArgs a, long long head, long long ngroups) {
     long long b = g0 / a.plane;
     unsigned p = (unsigned)(g0 - b * a.plane);
     float lo = 0.f, d = 0.f;
-    if (MODE != 2) lo = a.params[2 * b], d = a.params[2 * b + 1];
+    double vmin = a.vmin, den = a.den;
+    if (MODE < 2) lo = a.params[2 * b], d = a.params[2 * b + 1];
+    if (MODE == 3) ranged_axis(a, b, vmin, den);
     unsigned c[kGroup];
 #pragma unroll
     for (int j = 0; j < kGroup; ++j) {
       if (MODE != 2 && p == a.plane) {  // the next image starts inside the group
         p = 0, ++b;
-        lo = a.params[2 * b], d = a.params[2 * b + 1];
+        if (MODE < 2) lo = a.params[2 * b], d = a.params[2 * b + 1];
+        if (MODE == 3) ranged_axis(a, b, vmin, den);
       }
-      c[j] = s_lut[pixel_index<MODE>(x[j], lo, d, a)];
+      c[j] = s_lut[pixel_index<MODE>(x[j], lo, d, vmin, den, a)];
       ++p;
     }
     uint4* dst = reinterpret_cast<uint4*>(a.out + 3 * g0);
@@ -247,11 +268,13 @@ dc_color_scalar(ColorArgs a, long long s0, long long n0, long long s1, long long
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n0 + n1; i += stride) {
     const long long g = i < n0 ? s0 + i : s1 + (i - n0);
     float lo = 0.f, d = 0.f;
+    double vmin = a.vmin, den = a.den;
     if (MODE != 2) {
       const long long b = g / a.plane;
-      lo = a.params[2 * b], d = a.params[2 * b + 1];
+      if (MODE < 2) lo = a.params[2 * b], d = a.params[2 * b + 1];
+      if (MODE == 3) ranged_axis(a, b, vmin, den);
     }
-    const unsigned c = s_lut[pixel_index<MODE>(a.map[g], lo, d, a)];
+    const unsigned c = s_lut[pixel_index<MODE>(a.map[g], lo, d, vmin, den, a)];
     unsigned char* o = a.out + 3 * g;
     o[0] = (unsigned char)c, o[1] = (unsigned char)(c >> 8), o[2] = (unsigned char)(c >> 16);
   }
@@ -297,6 +320,7 @@ hipError_t launch_depth_colorize(const float* map, int B, int h, int w, int mode
   a.plane = (unsigned)h * (unsigned)w;
   a.inverse = map_is_inverse, a.swap_rb = swap_rb;
   a.vmin = 0.0, a.den = 1.0;
+  a.range = nullptr, a.range_stride = 0, a.positive_only = 0, a.reciprocal = 0;
   const long long total = (long long)B * a.plane;
   if (mode == 2) {
     if (vmax <= vmin) vmax = vmin + 1e-6;
@@ -320,6 +344,22 @@ hipError_t launch_depth_colorize(const float* map, int B, int h, int w, int mode
     launch_color<0>(a, total, st);
   else
     launch_color<1>(a, total, st);
+  return hipGetLastError();
+}
+
+// Checks nothing: the one caller, mde_op_depth_colorize_ranged in ops_abi.hip, has refused null pointers,
+// non-positive sizes, a negative range_stride, a misaligned range, a plane of 2^31 - 256 pixels or more
+// and batch > 65535.
+hipError_t launch_depth_colorize_ranged(const float* map, int B, int h, int w, int positive_only, int reciprocal,
+                                        const double* range, int range_stride, const unsigned char* lut, int swap_rb,
+                                        unsigned char* out, hipStream_t st) {
+  ColorArgs a;
+  a.map = map, a.out = out, a.lut = lut, a.params = nullptr;
+  a.plane = (unsigned)h * (unsigned)w;
+  a.inverse = 0, a.swap_rb = swap_rb;
+  a.vmin = 0.0, a.den = 1.0;
+  a.range = range, a.range_stride = range_stride, a.positive_only = positive_only, a.reciprocal = reciprocal;
+  launch_color<3>(a, (long long)B * a.plane, st);
   return hipGetLastError();
 }
 

@@ -239,6 +239,20 @@ size_t depth_colorize_ws_bytes(int B, int h, int w);
 hipError_t launch_depth_colorize(const float* map, int B, int h, int w, int mode, int map_is_inverse, double denom_eps,
                                  double vmin, double vmax, const unsigned char* lut257x3, int swap_rb,
                                  unsigned char* out, float* range_out, void* ws, hipStream_t st);
+// the same colour pass on an axis read from device memory (include/mde.h, mde_op_depth_colorize_ranged):
+// image b is drawn on range[b * range_stride], range[b * range_stride + 1].  One or two kernels
+hipError_t launch_depth_colorize_ranged(const float* map, int B, int h, int w, int positive_only, int reciprocal,
+                                        const double* range, int range_stride, const unsigned char* lut257x3,
+                                        int swap_rb, unsigned char* out, hipStream_t st);
+// depth_quantiles.hip: np.percentile (method linear) of the valid pixels of fp32 maps [B][h][w] by radix
+// select -> double out[rows][8] (include/mde.h, mde_op_depth_quantiles: counts, min, max, up to three
+// quantiles, the display range); q_percent is read on the host; ws = depth_quantiles_ws_bytes() of
+// 8-byte aligned scratch.  Enqueues eleven kernels, nothing else.  No argument checks
+// here: the ABI wrapper in ops_abi.hip holds the only copy of the limits
+size_t depth_quantiles_ws_bytes(int B, int h, int w);
+hipError_t launch_depth_quantiles(const float* map, int B, int h, int w, int positive_only, int reciprocal,
+                                  int pooled, int sample_cap, const double* q_percent, int nq, double* out, void* ws,
+                                  hipStream_t st);
 // preprocess_cubic.hip: cv2's uint8 INTER_CUBIC of [B][sh][pitch] 3-channel rows seen through a virtual
 // constant border of pad_* pixels (include/mde.h, mde_op_resize_cubic_u8; pad_rgb in output channel
 // order); lut == nullptr: dst uint8 NHWC [B][oh][ow][3]; else dst float NCHW [B][3][oh][ow] =

@@ -211,6 +211,45 @@ int mde_op_depth_colorize(const float* map, int batch, int h, int w, int mode, i
          "mde_op_depth_colorize");
 }
 
+int mde_op_depth_colorize_ranged(const float* map, int batch, int h, int w, int positive_only, int reciprocal,
+                                 const double* range_dev, int range_stride, const unsigned char* lut257x3,
+                                 int swap_rb, unsigned char* out_u8, void* st) {
+  const char* why = (!map || !out_u8 || !lut257x3 || !range_dev) ? "null pointer"
+                                                                  : depth_eval_geometry_error(batch, h, w);
+  if (!why && range_stride < 0) why = "range_stride is negative";
+  if (!why && (reinterpret_cast<uintptr_t>(range_dev) & 7)) why = "range_dev must be 8-byte aligned";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_depth_colorize_ranged: ") + why);
+  OP_RET(launch_depth_colorize_ranged(map, batch, h, w, positive_only != 0, reciprocal != 0, range_dev, range_stride,
+                                      lut257x3, swap_rb != 0, out_u8, (hipStream_t)st),
+         "mde_op_depth_colorize_ranged");
+}
+
+size_t mde_op_depth_quantiles_ws_bytes(int batch, int h, int w) {
+  if (depth_eval_geometry_error(batch, h, w)) return 0;  // the same limits: unsigned pixel index, grid.y
+  return depth_quantiles_ws_bytes(batch, h, w);
+}
+
+int mde_op_depth_quantiles(const float* map, int batch, int h, int w, int positive_only, int reciprocal, int pooled,
+                           int sample_cap, const double* q_percent, int nq, double* out, void* ws, size_t ws_bytes,
+                           void* st) {
+  const char* why = (!map || !q_percent || !out) ? "null pointer" : depth_eval_geometry_error(batch, h, w);
+  if (!why && (nq < 1 || nq > 3)) why = "nq must be 1, 2 or 3";
+  for (int i = 0; !why && i < nq; ++i)
+    if (!(q_percent[i] >= 0.0 && q_percent[i] <= 100.0)) why = "a q_percent outside [0, 100] (or NaN)";
+  if (!why && sample_cap < 0) why = "sample_cap is negative";
+  // batch <= 65535 and a plane below 2^31: the product fits 64 bits
+  if (!why && pooled && (long long)batch * h * w >= 0x80000000LL - 256)
+    why = "pooled: batch * h * w of 2^31 - 256 or more";
+  if (!why && (!ws || ws_bytes < depth_quantiles_ws_bytes(batch, h, w)))
+    why = "needs ws of mde_op_depth_quantiles_ws_bytes()";
+  if (!why && ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(out)) & 7))
+    why = "out and ws must be 8-byte aligned";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_depth_quantiles: ") + why);
+  OP_RET(launch_depth_quantiles(map, batch, h, w, positive_only != 0, reciprocal != 0, pooled != 0, sample_cap,
+                                q_percent, nq, out, ws, (hipStream_t)st),
+         "mde_op_depth_quantiles");
+}
+
 namespace {
 // the cubic resize indexes the source, the virtual (padded) and the destination plane with an int
 // and puts the batch on grid.y

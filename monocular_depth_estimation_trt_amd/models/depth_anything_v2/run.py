@@ -14,7 +14,7 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
         [--ply out.ply --f-px F [--ply-step N]]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
-        [--color out.png [--color-range VMIN VMAX]]
+        [--color out.png [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near]]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed -- taken through the

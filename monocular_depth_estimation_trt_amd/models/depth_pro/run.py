@@ -13,7 +13,7 @@
         [--input x.npy] [--src-hw H W] [--f-px F] [--host-preprocess] [--host-postprocess]
         [--ply out.ply] [--ply-step N]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
-        [--color out.png [--color-range VMIN VMAX]]
+        [--color out.png [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near]]
 
 `--image` is a source-resolution BGR photo -- a .npy holding a uint8 [H,W,3]
 BGR array, or an image file if Pillow is installed.  It is normalised and

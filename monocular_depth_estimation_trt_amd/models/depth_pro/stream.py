@@ -3,7 +3,7 @@ paths `models/depth_pro/onnx2trt_video.py` (:69-81) and `onnx2trt_webcam.py`
 (:96-104), whose output is the coloured frame and nothing else:
 
     python -m monocular_depth_estimation_trt_amd.models.depth_pro.stream \
-        --frames FRAMES.npy --out OUT.npy [--color-range VMIN VMAX] [--f-px F]
+        --frames FRAMES.npy --out OUT.npy [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near] [--f-px F]
         [--source synthetic:depth_pro | DepthPro.safetensors] [--engine PATH]
 
 `--frames` is a uint8 [T,H,W,3] BGR array; `--out` receives the uint8
@@ -49,6 +49,7 @@ def build_parser(model="depth_pro", size=None):
     ap.add_argument("--out", default="", metavar="OUT.npy", help="where the uint8 [T,H,W,3] BGR colour frames go")
     ap.add_argument("--color-range", type=float, nargs=2, default=None, metavar=("VMIN", "VMAX"),
                     help="draw depth on this fixed axis in metres instead of each frame's own range")
+    visualize.add_robust_arguments(ap)
     ap.add_argument("--f-px", type=float, default=None,
                     help="focal length in pixels instead of the predicted one")
     return ap
@@ -74,6 +75,8 @@ def main(argv=None, model="depth_pro"):
         raise SystemExit("--f-px must be positive")
     if a.color_range is not None and not all(v == v for v in a.color_range):
         raise SystemExit("--color-range must not be NaN")
+    if a.color_range is not None and visualize.robust_percent(a) is not None:
+        raise SystemExit("--color-robust and --color-range exclude each other")
     frames = load_frames(a.frames)
     T, H, W = frames.shape[:3]
     kw = visualize.color_kwargs(a, s)
@@ -102,6 +105,8 @@ def main(argv=None, model="depth_pro"):
                     dc.download(stream)  # the colour frame and its range; the one synchronisation
                     colour[t] = dc.result()[0]
                 dur_time = time.perf_counter() - t0
+                # the last frame's map is still on the card
+                dist = visualize.device_distribution(d_map.value, H, W, stream) if kw["mode"] == "robust" else None
                 f_host = np.empty(1, np.float32)
                 hip_call("mde_rt_memcpy_dtoh_async", f_host.ctypes.data_as(C.c_void_p), d_f, 4, C.c_void_p(stream))
                 stream_synchronize(stream)
@@ -119,6 +124,8 @@ def main(argv=None, model="depth_pro"):
     print(f"[MDET] Average inference time: {avg_time * 1000:.2f} [msec]")
     print(f"[MDET] focal_length : {f_last}")
     print(f"[MDET] color : mode {kw['mode']} (device; {T} frames of {H * W * 3} bytes came back, no float map) -> {a.out}")
+    if kw["mode"] == "robust":
+        print(visualize.format_distribution(dist))
     return colour
 
 

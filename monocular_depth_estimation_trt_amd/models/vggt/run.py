@@ -9,7 +9,7 @@
 
     python -m monocular_depth_estimation_trt_amd.models.vggt.run \
         [--source synthetic:vggt:vggt_1b:2468 | model.pt | model.safetensors]
-        [--image a.npy|a.jpg [b.npy ...]] [--host-preprocess] [--color out.png [--color-range VMIN VMAX]]
+        [--image a.npy|a.jpg [b.npy ...]] [--host-preprocess] [--color out.png [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near]]
         [--input x.npy] [--frames S] [--box x1 y1 x2 y2]
 
 `--image` is S source-resolution BGR photos of one size -- .npy files holding
@@ -140,11 +140,17 @@ def _device_crop(a, s, d_depth, frames, size, box, photo_hw, stream):
         depth = mem.host.reshape(frames, ch, cw).copy()
         if a.color:
             path = a.color
-            for i in range(frames):
-                a.color = _frame_path(path, i)
-                visualize.driver_color(a, s, mem.device + 4 * i * ch * cw, (ch, cw), stream, resize_hw=photo_hw,
-                                       denom_eps=1e-6)
-            a.color = path
+            # --color-robust: all views share one axis, pooled over the cropped maps
+            shared = visualize.pooled_range(a, s, mem.device, frames, (ch, cw), stream) if frames > 1 else None
+            try:
+                for i in range(frames):
+                    a.color = _frame_path(path, i)
+                    visualize.driver_color(a, s, mem.device + 4 * i * ch * cw, (ch, cw), stream, resize_hw=photo_hw,
+                                           denom_eps=1e-6, shared=shared)
+            finally:
+                a.color = path
+                if shared is not None:
+                    shared[0].free()
     finally:
         mem.free()
     return depth
