@@ -605,6 +605,69 @@ int mde_op_depth_quantiles(const float* map, int batch, int h, int w, int positi
 int mde_op_depth_colorize_ranged(const float* map, int batch, int h, int w, int positive_only, int reciprocal,
                                  const double* range_dev, int range_stride, const unsigned char* lut257x3,
                                  int swap_rb, unsigned char* out_u8, void* stream);
+/* Point-cloud preview (added to ABI 11 without a new version number, as the additions before it): the
+ * reference's core/viz.py:render_points, what demo.py:cloud_figure shows of a cloud -- an orthographic,
+ * z-buffered picture of the point cloud "viewed from above-left", centred on the per-axis median, scaled by
+ * the 99th percentile of the rotated |x|, |y|, the near point winning each pixel -- on the device, from the
+ * depth map, without the records or the float map leaving it.  depth, batch, h, w, step, photo, pitch,
+ * swap_rb, f_px_dev, fx, fy, cx, cy mean exactly what they mean for mde_op_point_cloud.  cos_a, sin_a, cos_e,
+ * sin_e are HOST doubles: the caller's np.cos / np.sin of the azimuth and the elevation in radians (the
+ * reference's defaults: elev -18, azim 24 degrees).  bg_rgb is a HOST int[3], 0..255, in R, G, B order (the
+ * reference's 22, 22, 26).  out_u8 is uint8 [batch][out_h][out_w][3], tightly packed; out_swap_rb != 0 writes
+ * B, G, R.  view_out is a device double[batch][8]; view_in is null or a device double[batch][8].  The contract,
+ * every operation rounded separately, never fused:
+ *   points      sample i of the hs x ws step grid has X, Y, Z as in mde_op_point_cloud (float32, organized
+ *               order); it is valid iff X, Y and Z are finite and Z > 0 (the reference's subsample_cloud).
+ *               Every valid sample is drawn: the reference's random thinning to 120000 points is NOT
+ *               reproduced, so parity with it is claimed for clouds up to that size (`step` gets a larger map
+ *               there)
+ *   centre      c[k] = percentile 50 of the valid X, Y, Z values respectively, as mde_op_depth_quantiles
+ *               computes a quantile (-0 counts as +0, float64 lerp).  np.median takes the mean of the two
+ *               middle values at an even count, (a + b) / 2; the lerp gives a + (b - a) * 0.5 (or its mirror),
+ *               which differs from it by at most one float64 rounding; at an odd count they are equal
+ *   rotation    float64, from the doubles of X, Y, Z:
+ *                 dx = X - c0, dy = Y - c1, dz = Z - c2
+ *                 x1 = cos_a * dx + sin_a * dz          z1 = (-sin_a) * dx + cos_a * dz
+ *                 y2 = cos_e * dy - sin_e * z1          z2 = sin_e * dy + cos_e * z1
+ *   span        percentile 99 of the 2 * n_valid float32 values (float)|x1|, (float)|y2| pooled, by the same
+ *               quantile arithmetic; 1.0 when that is not finite or <= 0
+ *   scale       (0.46 * min(out_h, out_w)) / span
+ *   pixel       u = rint(x1 * scale + out_w / 2.0), v = rint(y2 * scale + out_h / 2.0), half to even, float64;
+ *               inside iff 0 <= u < out_w and 0 <= v < out_h, tested on the doubles (a NaN is outside)
+ *   winner      of a pixel: among the valid samples inside it the smallest (float)z2, compared as floats with
+ *               -0 equal to +0 (the reference compares the doubles: a float32 z-test key is this op's); among
+ *               equal ones the lowest sample index.  Its colour is the photo's bytes of that sample, R, G, B
+ *               after swap_rb, or (200, 200, 200) without a photo.  A pixel with no sample gets bg_rgb
+ *   view_out[b] {n_valid, c0, c1, c2, span, scale, samples inside the picture, 0}; with no valid sample:
+ *               centre 0, span 1.0, nothing drawn
+ *   view_in     non-null: image b takes c0, c1, c2 and scale from view_in[b] (slots 1, 2, 3, 5), no selection
+ *               runs, and view_out[b] repeats slots 1..5 of view_in[b] with its own two counts -- the fixed
+ *               camera for a frame sequence.  view_in may be view_out
+ * Only the reference's default point_px = 1 is built (for larger values it lets later offsets paint over
+ * nearer points).  Without view_in the op writes X, Y, Z as three float32 planes (NaN where invalid) and
+ * selects the three medians with the kernels of mde_op_depth_quantiles, overwrites two planes with |x1|, |y2|
+ * and selects the span with one pooled call per image; then, in both cases, it clears a z-buffer
+ * uint64[batch][out_h * out_w] to all ones, every valid sample inside the picture does one 64-bit integer
+ * atomic min of (order-preserving key of (float)z2) << 32 | sample index, and one thread per pixel writes
+ * the winner's three bytes.  The only atomic is that integer min (the two counts are summed from per-workgroup
+ * slots), no workgroup waits on another's writes: the same bytes on every run.  Bytes past batch * out_h * out_w * 3 of out_u8 are not written.
+ * ws: mde_op_cloud_view_ws_bytes(...) bytes of device scratch (planes, z-buffer, quantile rows and
+ * scratch), 8-byte aligned (0 is returned for sizes the op refuses); its content on entry does not matter.
+ * The kernels are pinned to monocular_depth_estimation_trt_amd/pointcloud.py:render_np, the picture byte for
+ * byte and the view rows bit for bit; render_np against the reference's render_points: DESIGN.md,
+ * "Point-cloud preview".  mde_op_cloud_view only enqueues on `stream` (no allocation, no synchronisation, no
+ * host read of device memory: capturable).  MDE_ERR_ARG, before any device call: null depth, out_u8,
+ * view_out or bg_rgb; a non-positive size or step; a photo with pitch < 3 * w; f_px_dev null and fx <= 0 or
+ * fy <= 0; NaN cx or cy; h * w of 2^31 - 256 or more; hs * ws of 2^30 - 128 or more (two planes are pooled in
+ * one selection); batch > 21845 (three planes per image); a non-positive picture size or out_h * out_w of
+ * 2^31 - 256 or more; a NaN or infinite trig value; a background colour outside 0..255; ws null, ws_bytes too
+ * small; ws, view_in or view_out not 8-byte aligned. */
+size_t mde_op_cloud_view_ws_bytes(int batch, int h, int w, int step, int out_h, int out_w);
+int mde_op_cloud_view(const float* depth, int batch, int h, int w, int step, const unsigned char* photo, int pitch,
+                      int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, double cos_a,
+                      double sin_a, double cos_e, double sin_e, const double* view_in, const int* bg_rgb,
+                      int out_swap_rb, unsigned char* out_u8, int out_h, int out_w, double* view_out, void* ws,
+                      size_t ws_bytes, void* stream);
 /* VGGT photo path (added to ABI 11 without a new version number, as the three additions before it): the two
  * ends of reference models/vggt/onnx2trt.py (:32-53, :121-146) around the engine, over core/preprocess.py:
  * resize_square_pad -- cvtColor(BGR2RGB), copyMakeBorder(BORDER_CONSTANT, white) to a square, one

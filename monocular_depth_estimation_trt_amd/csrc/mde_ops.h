@@ -253,6 +253,19 @@ size_t depth_quantiles_ws_bytes(int B, int h, int w);
 hipError_t launch_depth_quantiles(const float* map, int B, int h, int w, int positive_only, int reciprocal,
                                   int pooled, int sample_cap, const double* q_percent, int nq, double* out, void* ws,
                                   hipStream_t st);
+// cloud_view.hip: an orthographic, z-buffered picture uint8 [B][out_h][out_w][3] of the cloud that
+// launch_point_cloud would pack (the same depth, photo and camera arguments), seen from the angles whose
+// cosines and sines the caller gives (include/mde.h, mde_op_cloud_view); view_out double[B][8]: the
+// counts, the centre, the span and the scale; view_in non-null: a fixed camera, no selection.  ws =
+// cloud_view_ws_bytes() of 8-byte aligned scratch.  Enqueues kernels (and launch_depth_quantiles, 1 + B
+// times, without view_in), nothing else.  No argument checks here: the ABI wrapper in ops_abi.hip holds
+// the only copy of the limits
+size_t cloud_view_ws_bytes(int B, int h, int w, int step, int out_h, int out_w);
+hipError_t launch_cloud_view(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
+                             int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, double cos_a,
+                             double sin_a, double cos_e, double sin_e, const double* view_in, const int bg_rgb[3],
+                             int out_swap_rb, unsigned char* out, int out_h, int out_w, double* view_out, void* ws,
+                             hipStream_t st);
 // preprocess_cubic.hip: cv2's uint8 INTER_CUBIC of [B][sh][pitch] 3-channel rows seen through a virtual
 // constant border of pad_* pixels (include/mde.h, mde_op_resize_cubic_u8; pad_rgb in output channel
 // order); lut == nullptr: dst uint8 NHWC [B][oh][ow][3]; else dst float NCHW [B][3][oh][ow] =

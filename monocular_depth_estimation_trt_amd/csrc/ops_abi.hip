@@ -157,6 +157,52 @@ int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, co
 }
 
 namespace {
+// what mde_op_cloud_view_ws_bytes can judge: the point-cloud op's geometry, the picture, and the limits of
+// the selection (three planes per image on grid.y; an image's two planes pooled in one quantile call)
+const char* cloud_view_geometry_error(int batch, int h, int w, int step, int out_h, int out_w) {
+  long long plane = 0;
+  if (const char* why = point_cloud_geometry_error(batch, h, w, step, &plane)) return why;
+  if (out_h < 1 || out_w < 1) return "the picture's sizes must be positive";
+  if ((long long)out_h * out_w >= 0x7fffffffLL - 256) return "a picture of 2^31 - 256 pixels or more";
+  if (plane >= 0x40000000LL - 128) return "a sampled grid of 2^30 - 128 samples or more";
+  if (batch > 21845) return "batch > 21845";
+  return nullptr;
+}
+}  // namespace
+
+size_t mde_op_cloud_view_ws_bytes(int batch, int h, int w, int step, int out_h, int out_w) {
+  if (cloud_view_geometry_error(batch, h, w, step, out_h, out_w)) return 0;
+  return cloud_view_ws_bytes(batch, h, w, step, out_h, out_w);
+}
+
+int mde_op_cloud_view(const float* depth, int batch, int h, int w, int step, const unsigned char* photo, int pitch,
+                      int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, double cos_a,
+                      double sin_a, double cos_e, double sin_e, const double* view_in, const int* bg_rgb,
+                      int out_swap_rb, unsigned char* out_u8, int out_h, int out_w, double* view_out, void* ws,
+                      size_t ws_bytes, void* st) {
+  const char* why = (!depth || !out_u8 || !view_out || !bg_rgb)
+                        ? "null pointer"
+                        : cloud_view_geometry_error(batch, h, w, step, out_h, out_w);
+  if (!why && photo && pitch < 3 * (long long)w) why = "pitch < 3 * w";
+  if (!why && !f_px_dev && !(fx > 0.f && fy > 0.f)) why = "f_px_dev is null and fx <= 0 or fy <= 0";
+  if (!why && !(cx == cx && cy == cy)) why = "cx or cy is NaN";
+  for (double t : {cos_a, sin_a, cos_e, sin_e})
+    if (!why && !(t - t == 0.0)) why = "a NaN or infinite trig value";
+  for (int c = 0; !why && c < 3; ++c)
+    if (bg_rgb[c] < 0 || bg_rgb[c] > 255) why = "background colour outside 0..255";
+  if (!why && (!ws || ws_bytes < cloud_view_ws_bytes(batch, h, w, step, out_h, out_w)))
+    why = "needs ws of mde_op_cloud_view_ws_bytes()";
+  if (!why && ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(view_in) |
+                reinterpret_cast<uintptr_t>(view_out)) & 7))
+    why = "ws, view_in and view_out must be 8-byte aligned";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_cloud_view: ") + why);
+  OP_RET(launch_cloud_view(depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy, cos_a, sin_a,
+                           cos_e, sin_e, view_in, bg_rgb, out_swap_rb != 0, out_u8, out_h, out_w, view_out, ws,
+                           (hipStream_t)st),
+         "mde_op_cloud_view");
+}
+
+namespace {
 const char* depth_eval_geometry_error(int batch, int h, int w) {
   if (batch < 1 || h < 1 || w < 1) return "batch and sizes must be positive";
   if ((long long)h * w >= 0x80000000LL - 256) return "a plane of 2^31 - 256 pixels or more";

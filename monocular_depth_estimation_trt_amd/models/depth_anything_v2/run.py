@@ -13,6 +13,7 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
         [--image photo.npy|photo.jpg] [--host-preprocess]
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
         [--ply out.ply --f-px F [--ply-step N]]
+        [--cloud-view out.png --f-px F [--cloud-view-size H W] [--cloud-view-angles ELEV AZIM] [--cloud-view-step N]]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
         [--color out.png [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near]]
 
@@ -40,6 +41,11 @@ driver's clamp [1e-3, 1e3] dropped.  There is no FOV head: `--f-px` (focal
 length in pixels at the source size) is required.  Relative models (the
 relative checkpoints, depth_anything_ac, distill_any_depth) are refused:
 relative depth is not turned into metres.
+
+`--cloud-view PATH` draws that cloud instead of packing it: the reference's
+core/viz.py:render_points (demo.py:cloud_figure), an orthographic, z-buffered
+picture seen from above-left, on the device (pointcloud.DeviceCloudView) under
+the same conditions as `--ply`; only the picture comes back.
 
 `--gt DEPTH.npy --gt-mask MASK.npy` scores the map against measured ground
 truth of the same size (the reference's tools/evaluate_gt.py:555-583 over its
@@ -69,6 +75,7 @@ import time
 import numpy as np
 
 from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, visualize, weights
+from monocular_depth_estimation_trt_amd import pointcloud
 from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
@@ -109,7 +116,9 @@ def build_parser(model="depth_anything_v2", mc=None):
     ap.add_argument("--ply", default="", metavar="PATH",
                     help="write the point cloud (binary PLY; colours from --image) of the metric depth; needs --f-px")
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
-    ap.add_argument("--f-px", type=float, default=None, help="with --ply: focal length in pixels at the source size")
+    ap.add_argument("--f-px", type=float, default=None,
+                    help="with --ply / --cloud-view: focal length in pixels at the source size")
+    pointcloud.add_cloud_view_arguments(ap)
     evaluate.add_gt_arguments(ap)
     visualize.add_color_arguments(ap)
     return ap
@@ -118,17 +127,17 @@ def build_parser(model="depth_anything_v2", mc=None):
 NOT_METRIC = "--ply needs a metric model: relative depth is not turned into metres"
 
 
-def _check_ply(a, mc):
-    """--ply's conditions that can be answered before an engine is built."""
+def _check_ply(a, mc, opt="--ply"):
+    """--ply's (and --cloud-view's) conditions that can be answered before an engine is built."""
     if a.f_px is None or not a.f_px > 0:
-        raise SystemExit("--ply needs --f-px (a positive focal length in pixels): this model predicts none")
-    if a.ply_step < 1:
+        raise SystemExit(f"{opt} needs --f-px (a positive focal length in pixels): this model predicts none")
+    if opt == "--ply" and a.ply_step < 1:
         raise SystemExit("--ply-step must be positive")
     fields = a.source.split(":")
     if mc["depth_type"] != "metric" or (fields[0] == "synthetic" and len(fields) > 2 and fields[2] == "relative"):
-        raise SystemExit(NOT_METRIC)
+        raise SystemExit(NOT_METRIC.replace("--ply", opt))
     if a.host_postprocess or mc["postprocess"] == "none":
-        raise SystemExit("--ply runs on the device post-process's depth map: not with --host-postprocess or a model "
+        raise SystemExit(f"{opt} runs on the device post-process's depth map: not with --host-postprocess or a model "
                          "without a post-process")
 
 
@@ -168,6 +177,9 @@ def main(argv=None, model="depth_anything_v2"):
         raise SystemExit("--host-preprocess needs --image")
     if a.ply:
         _check_ply(a, mc)
+    if a.cloud_view:
+        _check_ply(a, mc, "--cloud-view")
+        pointcloud.check_cloud_view_arguments(a)
     gt_policy = evaluate.check_gt_arguments(a, model_spec, device_map=not a.host_postprocess)
     visualize.check_color_arguments(a, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
@@ -177,6 +189,8 @@ def main(argv=None, model="depth_anything_v2"):
     gt_maps = evaluate.load_gt_arguments(a, gt_hw) if gt_policy else None
     if a.ply and img is not None and tuple(a.src_hw) != img.shape[:2]:
         raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
+    if a.cloud_view and img is not None and tuple(a.src_hw) != img.shape[:2]:
+        raise SystemExit("--cloud-view takes its colours from the --image photo: --src-hw must be the photo's size")
     if u8 and a.engine.endswith("_fp16.mdeng"):
         a.engine = a.engine[:-len("_fp16.mdeng")] + "_u8_fp16.mdeng"
     if img is not None and a.host_preprocess:
@@ -200,6 +214,8 @@ def main(argv=None, model="depth_anything_v2"):
             engine.create_execution_context() as context:
         if a.ply and not engine.info.metric:
             raise SystemExit(NOT_METRIC)
+        if a.cloud_view and not engine.info.metric:
+            raise SystemExit(NOT_METRIC.replace("--ply", "--cloud-view"))
         inputs, outputs, bindings, stream = allocate_buffers(engine, output_shape, profile_idx=0)
         if x is None:
             ms = _device_preprocess(img, model, (input_h, input_w), a.input_format, inputs[0], stream)
@@ -228,6 +244,8 @@ def main(argv=None, model="depth_anything_v2"):
                                        f_px=a.f_px, z_lo=1e-3, z_hi=1e3)
                     print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {a.src_hw[0]}x{a.src_hw[1]} step "
                           f"{a.ply_step} -> {a.ply} : {ms:0.3f} ms, {n} points")
+                if a.cloud_view:
+                    pointcloud.driver_cloud_view(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px)
                 if gt_policy:
                     evaluate.driver_score(a, model, gt_policy, gt_maps, pp.mem.device, gt_hw, stream)
                 if a.color:

@@ -12,6 +12,7 @@
         [--source synthetic:depth_pro | DepthPro.safetensors] [--image photo.npy|photo.jpg]
         [--input x.npy] [--src-hw H W] [--f-px F] [--host-preprocess] [--host-postprocess]
         [--ply out.ply] [--ply-step N]
+        [--cloud-view out.png [--cloud-view-size H W] [--cloud-view-angles ELEV AZIM] [--cloud-view-step N]]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
         [--color out.png [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near]]
 
@@ -37,6 +38,13 @@ photo (no colours with `--input` or the synthetic image).  It runs on the
 device (pointcloud.DevicePointCloud) on the depth map and the focal length the
 device post-process left there, drops depths outside [1e-4, 1e4] and downloads
 the PLY records; `--ply-step N` keeps every N-th pixel on both axes.
+
+`--cloud-view PATH` is the reference's `core/viz.py:render_points` (what
+`demo.py:cloud_figure` shows): an orthographic, z-buffered picture of that
+cloud seen from above-left, drawn on the device from the depth map
+(pointcloud.DeviceCloudView, `mde_op_cloud_view`); only the picture comes
+back.  One `[MDET] cloud view ...` line is printed; the file is written like
+`--color`'s.
 
 `--gt DEPTH.npy --gt-mask MASK.npy` scores the metric depth against measured
 ground truth of the source size (the reference's tools/evaluate_gt.py:555-583
@@ -66,6 +74,7 @@ import numpy as np
 from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, visualize, weights_depth_pro
 from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
                                                                stream_synchronize)
+from monocular_depth_estimation_trt_amd import pointcloud
 from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DepthProDevicePostprocess, depth_pro_postprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DepthProPreprocess, load_image_bgr,
@@ -103,6 +112,7 @@ def build_parser(model="depth_pro", size=None):
     ap.add_argument("--ply", default="", metavar="PATH",
                     help="write the point cloud (binary PLY; colours from --image) of the metric depth")
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
+    pointcloud.add_cloud_view_arguments(ap)
     evaluate.add_gt_arguments(ap)
     visualize.add_color_arguments(ap)
     ap.add_argument("--iterations", type=int, default=100)
@@ -152,14 +162,15 @@ def _device_preprocess(img, size, mem, stream):
         ev.free()
 
 
-def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None, color=None):
+def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None, color=None, cloud_view=None):
     """DepthProDevicePostprocess on the output bindings in place, timed with
     hipEvents (kernel + D2H of the depth map and the focal length); `ply` =
     (path, step, photo or None): then the point cloud of the map, while it is
     still on the device, with the focal length the post-process used (the
     fourth result, pointcloud.device_ply's; else None); `score`: called with
     the map's device pointer while it is still there (--gt); `color`: likewise
-    (--color)."""
+    (--color); `cloud_view`: likewise, with the device focal length as well
+    (--cloud-view)."""
     if f_px is None and len(outputs) < 2:
         raise SystemExit("this engine has no fov_deg output: pass --f-px")
     ev = _Events(stream)
@@ -180,6 +191,8 @@ def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=Non
                 score(pp.mem.device)
             if color:
                 color(pp.mem.device)
+            if cloud_view:
+                cloud_view(pp.mem.device, pp.f_px.device)
             return depth, f, ms, cloud
     finally:
         ev.free()
@@ -200,6 +213,10 @@ def main(argv=None, model="depth_pro"):
                          "--host-postprocess")
     if a.ply and a.ply_step < 1:
         raise SystemExit("--ply-step must be positive")
+    if a.cloud_view and a.host_postprocess:
+        raise SystemExit("--cloud-view runs on the device post-process's depth map: do not combine it with "
+                         "--host-postprocess")
+    pointcloud.check_cloud_view_arguments(a)
     gt_policy = evaluate.check_gt_arguments(a, s, device_map=not a.host_postprocess)
     visualize.check_color_arguments(a, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
@@ -222,6 +239,8 @@ def main(argv=None, model="depth_pro"):
     gt_maps = evaluate.load_gt_arguments(a, src_hw) if gt_policy else None
     if a.ply and img is not None and src_hw != img.shape[:2]:
         raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
+    if a.cloud_view and img is not None and src_hw != img.shape[:2]:
+        raise SystemExit("--cloud-view takes its colours from the --image photo: --src-hw must be the photo's size")
     output_shapes = (1, 1, size, size)
     with common.get_engine(a.source, a.engine, "fp16", None, input_hw=(size, size)) as engine, \
             engine.create_execution_context() as context:
@@ -246,9 +265,11 @@ def main(argv=None, model="depth_pro"):
             score = (lambda d_map: evaluate.driver_score(a, model, gt_policy, gt_maps, d_map, src_hw, stream)) if gt_policy \
                 else None
             color = (lambda d_map: visualize.driver_color(a, s, d_map, src_hw, stream)) if a.color else None
+            view = (lambda d_map, d_f: pointcloud.driver_cloud_view(a, d_map, src_hw, stream, img_bgr=img, d_f_px=d_f,
+                                                                    f_px=a.f_px)) if a.cloud_view else None
             depth, f_px, ms, cloud = _device_postprocess(outputs, size, src_hw, a.f_px, stream,
                                                          ply=(a.ply, a.ply_step, img) if a.ply else None, score=score,
-                                                         color=color)
+                                                         color=color, cloud_view=view)
             print(f"[MDET] postprocess (device, kernel + D2H, hipEvents) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{ms:0.3f} ms")
             if cloud:

@@ -4,6 +4,7 @@ paths `models/depth_pro/onnx2trt_video.py` (:69-81) and `onnx2trt_webcam.py`
 
     python -m monocular_depth_estimation_trt_amd.models.depth_pro.stream \
         --frames FRAMES.npy --out OUT.npy [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near] [--f-px F]
+        [--cloud-view-out VIEWS.npy [--cloud-view-size H W] [--cloud-view-angles ELEV AZIM] [--cloud-view-step N]]
         [--source synthetic:depth_pro | DepthPro.safetensors] [--engine PATH]
 
 `--frames` is a uint8 [T,H,W,3] BGR array; `--out` receives the uint8
@@ -22,16 +23,25 @@ sequence.  The reference's three closing lines are printed (iterations time,
 average FPS, average inference time: wall clock per frame, everything above
 included).  The FPS overlay (cv2.putText) and container I/O are not part of
 this driver: frames come from and go to .npy arrays.
+
+`--cloud-view-out VIEWS.npy` adds one point-cloud preview per frame (uint8
+[T,h,w,3] BGR, `run.py --cloud-view`'s picture): pointcloud.DeviceCloudView on
+the metric map, the focal length and the frame, all still in device memory,
+enqueued before the frame's one synchronisation.  The camera -- centre and
+scale -- is selected on the first frame and fixed from its view row for the
+rest, so the sequence does not jitter; neither the float map nor the cloud
+leaves the card.
 """
 
 import argparse
+import contextlib
 import ctypes as C
 import os
 import time
 
 import numpy as np
 
-from monocular_depth_estimation_trt_amd import common, spec, visualize
+from monocular_depth_estimation_trt_amd import common, pointcloud, spec, visualize
 from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, free_buffers, hip_call,
                                                                stream_synchronize)
 from monocular_depth_estimation_trt_amd.postprocess import dp_postprocess
@@ -52,6 +62,12 @@ def build_parser(model="depth_pro", size=None):
     visualize.add_robust_arguments(ap)
     ap.add_argument("--f-px", type=float, default=None,
                     help="focal length in pixels instead of the predicted one")
+    ap.add_argument("--cloud-view-out", default="", metavar="VIEWS.npy",
+                    help="where the uint8 [T,h,w,3] BGR point-cloud previews go (camera fixed from the first frame)")
+    ap.add_argument("--cloud-view-size", type=int, nargs=2, default=list(pointcloud.VIEW_SIZE), metavar=("H", "W"))
+    ap.add_argument("--cloud-view-angles", type=float, nargs=2, default=list(pointcloud.VIEW_ANGLES),
+                    metavar=("ELEV", "AZIM"))
+    ap.add_argument("--cloud-view-step", type=int, default=1, help="draw every N-th pixel on both axes")
     return ap
 
 
@@ -77,10 +93,14 @@ def main(argv=None, model="depth_pro"):
         raise SystemExit("--color-range must not be NaN")
     if a.color_range is not None and visualize.robust_percent(a) is not None:
         raise SystemExit("--color-robust and --color-range exclude each other")
+    a.cloud_view = a.cloud_view_out
+    pointcloud.check_cloud_view_arguments(a)
     frames = load_frames(a.frames)
     T, H, W = frames.shape[:3]
     kw = visualize.color_kwargs(a, s)
     colour = np.empty((T, H, W, 3), np.uint8)
+    views = np.empty((T, *a.cloud_view_size, 3), np.uint8) if a.cloud_view_out else None
+    view_rows = np.zeros((T, pointcloud.VIEW_ROW), np.float64)
     f_last = float("nan")
     with common.get_engine(a.source, a.engine, "fp16", None, input_hw=(size, size)) as engine, \
             engine.create_execution_context() as context:
@@ -94,7 +114,12 @@ def main(argv=None, model="depth_pro"):
             d_fov = outputs[1].device if a.f_px is None else 0
             hip_call("mde_rt_malloc", C.byref(d_map), H * W * 4)
             hip_call("mde_rt_malloc", C.byref(d_f), 4)
-            with DepthProPreprocess(H, W, size) as pre, visualize.DeviceColorize(1, H, W) as dc:
+            with contextlib.ExitStack() as stack:
+                pre = stack.enter_context(DepthProPreprocess(H, W, size))
+                dc = stack.enter_context(visualize.DeviceColorize(1, H, W))
+                cv = stack.enter_context(pointcloud.DeviceCloudView(1, H, W, a.cloud_view_size, colour=True,
+                                                                    step=a.cloud_view_step)) if views is not None \
+                    else None
                 t0 = time.perf_counter()
                 for t in range(T):
                     pre.run(frames[t], inputs[0].device, stream)
@@ -102,8 +127,15 @@ def main(argv=None, model="depth_pro"):
                     dp_postprocess(outputs[0].device, 1, size, size, d_fov, a.f_px or 0.0, d_f.value, d_map.value, H, W,
                                    stream)
                     dc.enqueue(d_map.value, stream, **kw)
+                    if cv is not None:  # the frame is still in pre.mem.device; frames after the first keep its camera
+                        cv.enqueue(d_map.value, stream, d_photo=pre.mem.device, pitch=3 * W, swap_rb=True,
+                                   d_f_px=d_f.value, elev_deg=a.cloud_view_angles[0], azim_deg=a.cloud_view_angles[1],
+                                   d_view=cv.views.device if t else 0, out_swap_rb=True)
+                        cv.download(stream, sync=False)
                     dc.download(stream)  # the colour frame and its range; the one synchronisation
                     colour[t] = dc.result()[0]
+                    if cv is not None:
+                        views[t], view_rows[t] = cv.result()[0], cv.view()[0]
                 dur_time = time.perf_counter() - t0
                 # the last frame's map is still on the card
                 dist = visualize.device_distribution(d_map.value, H, W, stream) if kw["mode"] == "robust" else None
@@ -118,6 +150,9 @@ def main(argv=None, model="depth_pro"):
             free_buffers(inputs, outputs, stream)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.save(a.out, colour)
+    if views is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(a.cloud_view_out)), exist_ok=True)
+        np.save(a.cloud_view_out, views)
     avg_time = dur_time / T
     print(f"[MDET] {T} iterations time ({(1, 3, size, size)}): {dur_time:.4f} [sec]")
     print(f"[MDET] Average FPS: {1 / avg_time:.2f} [fps]")
@@ -126,6 +161,12 @@ def main(argv=None, model="depth_pro"):
     print(f"[MDET] color : mode {kw['mode']} (device; {T} frames of {H * W * 3} bytes came back, no float map) -> {a.out}")
     if kw["mode"] == "robust":
         print(visualize.format_distribution(dist))
+    if views is not None:
+        print(f"[MDET] cloud view (device; {T} previews of {views[0].nbytes} bytes came back, camera of frame 0: "
+              f"scale {view_rows[0][pointcloud.V_SCALE]!r}) {H}x{W} step {a.cloud_view_step} -> "
+              f"{a.cloud_view_size[0]}x{a.cloud_view_size[1]} {a.cloud_view_out} : valid points "
+              f"{[int(r[pointcloud.V_NVALID]) for r in view_rows]}, inside the picture "
+              f"{[int(r[pointcloud.V_INSIDE]) for r in view_rows]}")
     return colour
 
 

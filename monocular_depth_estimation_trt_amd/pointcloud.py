@@ -10,6 +10,14 @@ vertex records, so the D2H copy carries the file's body.
 kernels are held to it bit for bit), `DevicePointCloud` owns the buffers and
 drives the op, `write_ply` / `read_ply` put the records into a file and read
 them back.
+
+The preview of that cloud -- the reference's `core/viz.py:render_points`, what
+`demo.py:cloud_figure` shows: an orthographic, z-buffered picture seen from
+above-left -- is `mde_op_cloud_view` (csrc/cloud_view.hip), drawn from the
+depth map without the records leaving the device.  `render_np` restates its
+contract in numpy (the kernels are held to it, the picture byte for byte and
+the view row bit for bit), `DeviceCloudView` owns the buffers and drives the
+op, `device_cloud_view` is what the drivers' `--cloud-view` calls.
 """
 
 from __future__ import annotations
@@ -240,6 +248,307 @@ def device_ply(path, d_depth: int, h: int, w: int, stream: int, step: int = 1, i
                 _lib.call("mde_rt_event_destroy", e)
 
 
+VIEW_ROW = 8             # doubles per view row of mde_op_cloud_view
+# view_out[b][.] of mde_op_cloud_view (include/mde.h)
+V_NVALID, V_C0, V_C1, V_C2, V_SPAN, V_SCALE, V_INSIDE = range(7)
+VIEW_SIZE = (320, 420)   # core/viz.py:render_points' defaults
+VIEW_ANGLES = (-18.0, 24.0)
+VIEW_BG = (22, 22, 26)
+VIEW_GREY = 200          # the colour of a cloud without a photo
+
+
+def view_trig(elev_deg: float, azim_deg: float):
+    """(cos_a, sin_a, cos_e, sin_e) as the reference forms them: np.cos / np.sin
+    of np.deg2rad of the azimuth and the elevation."""
+    a, e = np.deg2rad(np.float64(azim_deg)), np.deg2rad(np.float64(elev_deg))
+    return float(np.cos(a)), float(np.sin(a)), float(np.cos(e)), float(np.sin(e))
+
+
+def _order_key(x32: np.ndarray) -> np.ndarray:
+    """The order-preserving uint32 key of float32 values (csrc/depth_quantiles.hip's
+    plain key): -0 counts as +0."""
+    u = np.ascontiguousarray(x32, dtype=np.float32).view(np.uint32).copy()
+    u[u == 0x80000000] = 0
+    neg = (u & np.uint32(0x80000000)) != 0
+    return np.where(neg, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def render_np(depth, fx, fy, cx, cy, size=VIEW_SIZE, elev_deg=VIEW_ANGLES[0], azim_deg=VIEW_ANGLES[1], photo=None,
+              swap_rb=False, step=1, view=None, bg=VIEW_BG):
+    """The include/mde.h contract of mde_op_cloud_view for one image, in numpy:
+    the reference's core/viz.py:render_points on the cloud of `unproject_np`,
+    with the centre and the span from `visualize.quantiles_np` and a packed
+    64-bit minimum for the z-test.  Returns (picture uint8 [out_h, out_w, 3]
+    in R, G, B order, view row float64 [8]).  `view`: a view row whose centre
+    and scale (slots 1, 2, 3, 5) are used instead of selecting them."""
+    from .visualize import Q_NVALID, Q_Q0, quantiles_np
+    out_h, out_w = int(size[0]), int(size[1])
+    if out_h < 1 or out_w < 1:
+        raise ValueError("the picture's sizes must be positive")
+    rec = unproject_np(depth, fx, fy, cx, cy, photo=photo, swap_rb=swap_rb, step=step)
+    h, w = np.asarray(depth).shape
+    hs, ws = grid(h, w, step)
+    X, Y, Z = rec["x"], rec["y"], rec["z"]
+    cos_a, sin_a, cos_e, sin_e = (np.float64(t) for t in view_trig(elev_deg, azim_deg))
+    row = np.zeros(VIEW_ROW, np.float64)
+    with np.errstate(all="ignore"):
+        valid = np.isfinite(X) & np.isfinite(Y) & np.isfinite(Z) & (Z > 0)
+
+        def rotate(c):
+            dx, dy, dz = X.astype(np.float64) - c[0], Y.astype(np.float64) - c[1], Z.astype(np.float64) - c[2]
+            x1 = cos_a * dx + sin_a * dz
+            z1 = (-sin_a) * dx + cos_a * dz
+            y2 = cos_e * dy - sin_e * z1
+            z2 = sin_e * dy + cos_e * z1
+            return x1, y2, z2
+
+        if view is not None:
+            view = np.asarray(view, dtype=np.float64).reshape(VIEW_ROW)
+            c, span, scale = view[V_C0:V_C2 + 1].copy(), view[V_SPAN], view[V_SCALE]
+        elif not valid.any():
+            c, span = np.zeros(3, np.float64), np.float64(1.0)
+            scale = np.float64(0.46 * min(out_h, out_w)) / span
+        else:
+            planes = np.where(valid[None], np.stack([X, Y, Z]), np.float32(np.nan)).reshape(3, hs, ws)
+            q = quantiles_np(planes, (50.0,))
+            assert q[0][Q_NVALID] == valid.sum()
+            c = q[:, Q_Q0].copy()
+            x1, y2, _ = rotate(c)
+            pool = np.where(valid[None], np.stack([np.abs(x1), np.abs(y2)]).astype(np.float32), np.float32(np.nan))
+            span = quantiles_np(pool.reshape(2, hs, ws), (99.0,), pooled=True)[0][Q_Q0]
+            if not np.isfinite(span) or span <= 0:
+                span = np.float64(1.0)
+            scale = np.float64(0.46 * min(out_h, out_w)) / span
+        x1, y2, z2 = rotate(c)
+        u = np.rint(x1 * scale + out_w / 2.0)
+        v = np.rint(y2 * scale + out_h / 2.0)
+        inside = valid & (u >= 0) & (u < out_w) & (v >= 0) & (v < out_h)
+        idx = np.flatnonzero(inside)
+        pixel = v[idx].astype(np.int64) * out_w + u[idx].astype(np.int64)
+        packed = (_order_key(z2[idx].astype(np.float32)).astype(np.uint64) << np.uint64(32)) | idx.astype(np.uint64)
+    empty = np.uint64(0xFFFFFFFFFFFFFFFF)
+    zbuf = np.full(out_h * out_w, empty, np.uint64)
+    np.minimum.at(zbuf, pixel, packed)
+    hit = zbuf != empty
+    win = (zbuf[hit] & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    pic = np.empty((out_h * out_w, 3), np.uint8)
+    pic[:] = np.asarray(bg, np.uint8)
+    if photo is not None:
+        pic[hit] = np.stack([rec["red"][win], rec["green"][win], rec["blue"][win]], axis=-1)
+    else:
+        pic[hit] = VIEW_GREY
+    row[V_NVALID], row[V_C0:V_C2 + 1], row[V_SPAN], row[V_SCALE], row[V_INSIDE] = valid.sum(), c, span, scale, idx.size
+    return pic.reshape(out_h, out_w, 3), row
+
+
+def cloud_view_ws_bytes(batch: int, h: int, w: int, step: int, out_h: int, out_w: int) -> int:
+    """Device scratch mde_op_cloud_view needs (mde_op_cloud_view_ws_bytes); 0: refused."""
+    return int(_lib.lib().mde_op_cloud_view_ws_bytes(int(batch), int(h), int(w), int(step), int(out_h), int(out_w)))
+
+
+def cloud_view(d_depth: int, batch: int, h: int, w: int, step: int, d_photo: int, pitch: int, swap_rb: bool,
+               d_f_px: int, fx: float, fy: float, cx: float, cy: float, trig, d_view_in: int, bg, out_swap_rb: bool,
+               d_out: int, out_h: int, out_w: int, d_view_out: int, d_ws: int, ws_nbytes: int, stream: int = 0) -> None:
+    """Device pointers in/out, enqueued on `stream` (mde_op_cloud_view); trig =
+    (cos_a, sin_a, cos_e, sin_e), e.g. view_trig(elev_deg, azim_deg)."""
+    _lib.call("mde_op_cloud_view", C.c_void_p(int(d_depth or 0)), int(batch), int(h), int(w), int(step),
+              C.c_void_p(int(d_photo or 0)), int(pitch), int(bool(swap_rb)), C.c_void_p(int(d_f_px or 0)),
+              float(fx), float(fy), float(cx), float(cy), *(float(t) for t in trig), C.c_void_p(int(d_view_in or 0)),
+              (C.c_int * 3)(*(int(c) for c in bg)), int(bool(out_swap_rb)), C.c_void_p(int(d_out or 0)), int(out_h),
+              int(out_w), C.c_void_p(int(d_view_out or 0)), C.c_void_p(int(d_ws or 0)), int(ws_nbytes),
+              C.c_void_p(int(stream or 0)))
+
+
+class DeviceCloudView:
+    """Owns the pictures uint8 [batch][out_h][out_w][3] and the view rows
+    float64 [batch][8] (device + pinned host) and the scratch of
+    mde_op_cloud_view for `batch` depth maps [h, w], with or without colour,
+    sampling every `step`-th pixel.
+
+    enqueue(d_depth, stream, ...) only enqueues (capturable) -- with `view=`,
+    a host array of view rows, one small H2D copy from pinned memory comes
+    first; download(stream) brings the pictures and the view rows back and
+    synchronizes; result() is the [batch, out_h, out_w, 3] pictures and view()
+    the [batch, 8] rows, valid until the next download; run() = enqueue,
+    download, result."""
+
+    def __init__(self, batch: int, h: int, w: int, out_hw=VIEW_SIZE, colour: bool = True, step: int = 1):
+        self.batch, self.h, self.w, self.step = int(batch), int(h), int(w), int(step)
+        self.out_h, self.out_w = int(out_hw[0]), int(out_hw[1])
+        self.colour = bool(colour)
+        self.pictures: Optional[HostDeviceMem] = None
+        self.views: Optional[HostDeviceMem] = None
+        self.view_in: Optional[HostDeviceMem] = None
+        self._ws = 0
+        self._ws_bytes = cloud_view_ws_bytes(self.batch, self.h, self.w, self.step, self.out_h, self.out_w)
+        if self._ws_bytes == 0:
+            raise ValueError(f"mde_op_cloud_view does not take batch {batch}, {h}x{w}, step {step}, picture "
+                             f"{self.out_h}x{self.out_w}")
+        try:
+            self.pictures = HostDeviceMem(self.batch * self.out_h * self.out_w * 3, np.uint8)
+            self.views = HostDeviceMem(self.batch * VIEW_ROW, np.dtype(np.float64))
+            self.view_in = HostDeviceMem(self.batch * VIEW_ROW, np.dtype(np.float64))
+            p = C.c_void_p()
+            _lib.call("mde_rt_malloc", C.byref(p), self._ws_bytes)
+            self._ws = int(p.value)
+        except Exception:
+            self.free()
+            raise
+
+    def enqueue(self, d_depth: int, stream: int, d_photo: int = 0, pitch: int = 0, swap_rb: bool = False,
+                d_f_px: int = 0, fx: Optional[float] = None, fy: Optional[float] = None,
+                cx: Optional[float] = None, cy: Optional[float] = None, elev_deg: float = VIEW_ANGLES[0],
+                azim_deg: float = VIEW_ANGLES[1], view=None, d_view: int = 0, bg=VIEW_BG,
+                out_swap_rb: bool = False) -> None:
+        """The kernels on `stream`.  Focal lengths and cx, cy as for
+        DevicePointCloud.enqueue.  `view`: host view rows [batch, 8] (or one
+        row for all) whose centre and scale fix the camera; `d_view`: the same
+        already in device memory -- `self.views.device` keeps the camera of
+        the previous enqueue."""
+        if self.pictures is None:
+            raise RuntimeError("DeviceCloudView already freed")
+        if bool(d_photo) != self.colour:
+            raise ValueError("DeviceCloudView(colour=%s) %s a photo" % (self.colour, "needs" if self.colour else
+                                                                        "does not take"))
+        if not d_f_px and fx is None:
+            raise ValueError("DeviceCloudView.enqueue needs d_f_px or fx")
+        if view is not None and d_view:
+            raise ValueError("DeviceCloudView.enqueue takes view or d_view, not both")
+        fx = 0.0 if fx is None else float(fx)
+        fy = fx if fy is None else float(fy)
+        if view is not None:
+            rows = np.broadcast_to(np.asarray(view, dtype=np.float64).reshape(-1, VIEW_ROW), (self.batch, VIEW_ROW))
+            self.view_in.host = np.ascontiguousarray(rows).reshape(-1)
+            _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(self.view_in.device),
+                      self.view_in.host.ctypes.data_as(C.c_void_p), self.view_in.nbytes, C.c_void_p(int(stream or 0)))
+            d_view = self.view_in.device
+        cloud_view(d_depth, self.batch, self.h, self.w, self.step, d_photo, pitch or 3 * self.w, swap_rb, d_f_px, fx,
+                   fy, self.w / 2 if cx is None else cx, self.h / 2 if cy is None else cy,
+                   view_trig(elev_deg, azim_deg), d_view, bg, out_swap_rb, self.pictures.device, self.out_h,
+                   self.out_w, self.views.device, self._ws, self._ws_bytes, stream)
+
+    def download(self, stream: int, sync: bool = True) -> None:
+        """The pictures and the view rows; synchronizes `stream` unless `sync`
+        is off (the caller's own synchronisation then makes them valid)."""
+        if self.pictures is None:
+            raise RuntimeError("DeviceCloudView already freed")
+        s = C.c_void_p(int(stream or 0))
+        for m in (self.pictures, self.views):
+            _lib.call("mde_rt_memcpy_dtoh_async", m.host.ctypes.data_as(C.c_void_p), C.c_void_p(m.device), m.nbytes, s)
+        if sync:
+            stream_synchronize(stream)
+
+    def result(self) -> np.ndarray:
+        """uint8 [batch, out_h, out_w, 3]; valid after download()."""
+        if self.pictures is None:
+            raise RuntimeError("DeviceCloudView already freed")
+        return self.pictures.host.reshape(self.batch, self.out_h, self.out_w, 3)
+
+    def view(self) -> np.ndarray:
+        """float64 [batch, 8] view rows; valid after download()."""
+        if self.views is None:
+            raise RuntimeError("DeviceCloudView already freed")
+        return self.views.host.reshape(self.batch, VIEW_ROW)
+
+    def run(self, d_depth: int, stream: int, **kw) -> np.ndarray:
+        self.enqueue(d_depth, stream, **kw)
+        self.download(stream)
+        return self.result()
+
+    def free(self) -> None:
+        for m in (self.pictures, self.views, self.view_in):
+            if m is not None:
+                m.free()
+        self.pictures = self.views = self.view_in = None
+        if self._ws:
+            _lib.call("mde_rt_free", C.c_void_p(self._ws))
+            self._ws = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+def device_cloud_view(path, d_depth: int, h: int, w: int, stream: int, size=VIEW_SIZE, elev_deg: float = VIEW_ANGLES[0],
+                      azim_deg: float = VIEW_ANGLES[1], step: int = 1, img_bgr: Optional[np.ndarray] = None,
+                      d_f_px: int = 0, f_px: Optional[float] = None):
+    """What the model drivers' --cloud-view does: DeviceCloudView on one device
+    depth map [h][w] at `d_depth`, with the given `f_px` or else the device
+    focal length `d_f_px`, cx, cy = w / 2, h / 2, colours from the BGR photo
+    `img_bgr` [h, w, 3] (uploaded here, once, before the timed part); the BGR
+    picture goes to `path` through visualize.save_image.  Returns (ms of the
+    kernels + D2H between two hipEvents on `stream`, the view row)."""
+    from .visualize import save_image
+    if img_bgr is not None and (img_bgr.dtype != np.uint8 or img_bgr.shape != (h, w, 3)):
+        raise ValueError(f"the photo must be uint8 [{h}, {w}, 3], got {img_bgr.dtype} {img_bgr.shape}")
+    s = C.c_void_p(int(stream or 0))
+    photo = None
+    ev = [C.c_void_p(), C.c_void_p()]
+    try:
+        for e in ev:
+            _lib.call("mde_rt_event_create", C.byref(e))
+        if img_bgr is not None:
+            photo = HostDeviceMem(h * w * 3, np.uint8)
+            photo.host = np.ascontiguousarray(img_bgr).reshape(-1)
+            _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(photo.device), photo.host.ctypes.data_as(C.c_void_p),
+                      photo.nbytes, s)
+        with DeviceCloudView(1, h, w, size, colour=photo is not None, step=step) as cv:
+            _lib.call("mde_rt_event_record", ev[0], s)
+            cv.enqueue(d_depth, stream, d_photo=photo.device if photo else 0, pitch=3 * w, swap_rb=True,
+                       d_f_px=0 if f_px is not None else d_f_px, fx=f_px, elev_deg=elev_deg, azim_deg=azim_deg,
+                       out_swap_rb=True)
+            cv.download(stream)
+            _lib.call("mde_rt_event_record", ev[1], s)
+            stream_synchronize(stream)
+            save_image(str(path), cv.result()[0])
+            ms = C.c_float()
+            _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
+            return float(ms.value), cv.view()[0].copy()
+    finally:
+        if photo is not None:
+            photo.free()
+        for e in ev:
+            if e:
+                _lib.call("mde_rt_event_destroy", e)
+
+
+def add_cloud_view_arguments(ap) -> None:
+    """The drivers' --cloud-view options."""
+    ap.add_argument("--cloud-view", default="", metavar="PATH",
+                    help="write a z-buffered orthographic picture of the point cloud (colours from --image)")
+    ap.add_argument("--cloud-view-size", type=int, nargs=2, default=list(VIEW_SIZE), metavar=("H", "W"))
+    ap.add_argument("--cloud-view-angles", type=float, nargs=2, default=list(VIEW_ANGLES), metavar=("ELEV", "AZIM"),
+                    help="degrees; the default looks from above-left")
+    ap.add_argument("--cloud-view-step", type=int, default=1, help="draw every N-th pixel on both axes")
+
+
+def check_cloud_view_arguments(a) -> None:
+    """--cloud-view's conditions that need no engine."""
+    if not a.cloud_view:
+        return
+    if min(a.cloud_view_size) < 1:
+        raise SystemExit("--cloud-view-size must be positive")
+    if a.cloud_view_step < 1:
+        raise SystemExit("--cloud-view-step must be positive")
+    if not all(np.isfinite(v) for v in a.cloud_view_angles):
+        raise SystemExit("--cloud-view-angles must be finite")
+
+
+def driver_cloud_view(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None):
+    """The drivers' --cloud-view: the picture of the device map [hw] at
+    `d_depth` and its `[MDET] cloud view ...` line.  Returns the view row."""
+    ms, row = device_cloud_view(a.cloud_view, d_depth, hw[0], hw[1], stream, size=a.cloud_view_size,
+                                elev_deg=a.cloud_view_angles[0], azim_deg=a.cloud_view_angles[1],
+                                step=a.cloud_view_step, img_bgr=img_bgr, d_f_px=d_f_px, f_px=f_px)
+    print(f"[MDET] cloud view (device, kernels + D2H, hipEvents) {hw[0]}x{hw[1]} step {a.cloud_view_step} -> "
+          f"{a.cloud_view_size[0]}x{a.cloud_view_size[1]} {a.cloud_view} : {ms:0.3f} ms, {int(row[V_NVALID])} valid "
+          f"points, {int(row[V_INSIDE])} inside the picture")
+    return row
+
+
 def ply_header(count: int, colour: bool) -> bytes:
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {int(count)}"]
     lines += [f"property {_PLY_TYPE[np.dtype(t).str]} {name}" for name, t in _XYZ + (_RGB if colour else [])]
@@ -280,4 +589,5 @@ def read_ply(path) -> np.ndarray:
 
 
 __all__ = ["vertex_dtype", "grid", "unproject_np", "ws_bytes", "point_cloud", "DevicePointCloud", "device_ply", "ply_header",
-           "write_ply", "read_ply"]
+           "write_ply", "read_ply", "view_trig", "render_np", "cloud_view_ws_bytes", "cloud_view", "DeviceCloudView",
+           "device_cloud_view", "add_cloud_view_arguments", "check_cloud_view_arguments", "driver_cloud_view"]
