@@ -461,6 +461,46 @@ int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, co
                        int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
                        float z_lo, float z_hi, void* records, size_t records_bytes, int* counts, void* ws,
                        size_t ws_bytes, void* stream);
+/* Meshes (added to ABI 11 without a new version number, as the point cloud was): the tail of reference
+ * models/metric_anything/demo_pointcloud.py (:142-149) -- drop the depth edges (the flying pixels a bilinear
+ * resize leaves at an occlusion boundary), then a triangle mesh over what is left, without unreferenced
+ * vertices -- on the device.  The arguments up to z_hi mean exactly what they mean for mde_op_point_cloud:
+ * the sampled grid hs x ws, the unprojection, the 12- or 15-byte vertex records, image b's vertex region at
+ * byte b * hs * ws * rec of `vertices`.  On the sampled grid, all float32:
+ *   valid(i, j) = z == z && z >= z_lo && z <= z_hi
+ *   edge        zmax and zmin over the valid samples of the 3 x 3 neighbourhood of (i, j) clipped to the grid,
+ *               diff = zmax - zmin (one subtraction);
+ *               edge = valid && ((edge_atol > 0 && diff > edge_atol) || (edge_rtol > 0 && diff / z > edge_rtol)),
+ *               IEEE division, strict comparisons (a sample exactly at the threshold is not an edge); both
+ *               tolerances 0: nothing is an edge
+ *   clean       valid && !edge
+ *   quads       (i, j) for i < hs - 1, j < ws - 1, corners a = (i, j), b = (i, j + 1), c = (i + 1, j + 1),
+ *               d = (i + 1, j); kept iff all four corners are clean
+ *   diagonal    fabsf(za - zc) <= fabsf(zb - zd): triangles (a, d, c) and (a, c, b); else (a, d, b) and
+ *               (b, d, c).  In the camera frame (X right, Y down, Z forward) every triangle faces the origin
+ *   vertices    faces != 0: a sample is a vertex iff at least one of its up to four quads is kept; faces == 0:
+ *               iff it is clean (the flying-pixel filter for a plain cloud; face_records and face_counts may
+ *               then be null).  Records dense, in row-major sample order; vertex_counts[b] their number
+ *   faces       record = uchar 3, int32 i0, i1, i2: 13 bytes, tightly packed (a PLY `property list uchar int
+ *               vertex_indices` entry), indices into image b's own vertex list; dense, in row-major quad order, a
+ *               quad's two triangles adjacent in the order above; image b's region starts at byte
+ *               b * 2 * (hs - 1) * (ws - 1) * 13 of `face_records`; face_counts[b] = number of triangles
+ * The same bytes on every run; no byte of either region past its count is written and none outside the
+ * regions; base pointers of any alignment.  hs < 2 or ws < 2 gives zero faces (and, with faces, zero vertices).
+ * Six kernels (four without faces) that need ws, mde_op_depth_mesh_ws_bytes(batch, h, w, step) bytes of device
+ * scratch, 4-byte aligned (0 is returned for sizes the op refuses): two ints per 1024 samples, and an int32
+ * index and a flag byte per sample.  The kernels are pinned byte for byte to
+ * monocular_depth_estimation_trt_amd/pointcloud.py:mesh_np.  mde_op_depth_mesh only enqueues on `stream` (no
+ * allocation, no synchronisation, no host read of a count: capturable).  MDE_ERR_ARG, before any device call:
+ * everything mde_op_point_cloud refuses in compact mode (of vertices, vertex_counts, vertices_bytes); a negative
+ * or NaN tolerance; faces != 0 with null face_records or face_counts, faces_bytes < batch * 2 * (hs - 1) *
+ * (ws - 1) * 13, or 2 * (hs - 1) * (ws - 1) of 2^31 - 256 or more; ws null, short or not 4-byte aligned. */
+size_t mde_op_depth_mesh_ws_bytes(int batch, int h, int w, int step);
+int mde_op_depth_mesh(const float* depth, int batch, int h, int w, int step, const unsigned char* photo, int pitch,
+                      int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, float z_lo,
+                      float z_hi, float edge_rtol, float edge_atol, int faces, void* vertices, size_t vertices_bytes,
+                      int* vertex_counts, void* face_records, size_t faces_bytes, int* face_counts, void* ws,
+                      size_t ws_bytes, void* stream);
 /* Depth evaluation (added to ABI 11 without a new version number, as the point cloud was): the per-image
  * call sequence of reference tools/evaluate_gt.py:555-583 over core/gt.py (orientation, align, metrics), on
  * the device.  pred and gt are fp32 [batch][h][w] (pred: the output of mde_op_depth_postprocess /

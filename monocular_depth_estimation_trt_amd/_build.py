@@ -23,7 +23,7 @@ ARCH = os.environ.get("MDE_OFFLOAD_ARCH", "gfx950")
 SOURCES = ["gemm.hip", "conv.hip", "attention.hip", "elementwise.hip", "engine.hip", "ops_abi.hip",
            "depth_pro.hip", "depth_pro_ops.hip", "gemm256.hip", "gemm_panel.hip", "vggt.hip", "vggt_ops.hip", "tuning.hip", "fp32.hip",
            "preprocess.hip", "depth_pro_photo.hip", "point_cloud.hip", "depth_eval.hip", "depth_colorize.hip",
-           "preprocess_cubic.hip", "depth_quantiles.hip", "cloud_view.hip"]
+           "preprocess_cubic.hip", "depth_quantiles.hip", "cloud_view.hip", "depth_mesh.hip"]
 # attention / conv: no NaN inputs by construction (masked keys are -inf, never
 # NaN; activations finite); lets fmaxf / the ReLUs lower to a bare v_max
 # without canonicalising moves (v_pk_max_f16 x, x before every f16 ReLU)
@@ -34,12 +34,14 @@ SOURCES = ["gemm.hip", "conv.hip", "attention.hip", "elementwise.hip", "engine.h
 # same for the float32 (v - lo) / d * 256 of the colour recipes;
 # preprocess_cubic: the same for cv2's cubic coefficients, Horner steps each
 # rounded on its own; depth_quantiles: numpy's float64 lerp a + d * g rounds twice;
-# cloud_view: the same for the float64 rotation and x1 * scale + w / 2 of the splat
+# cloud_view: the same for the float64 rotation and x1 * scale + w / 2 of the splat;
+# depth_mesh: the same for the unprojection and the edge rule's diff / z
 PER_FILE = {"attention.hip": ["-fno-honor-nans"], "conv.hip": ["-fno-honor-nans"],
             "preprocess.hip": ["-ffp-contract=off"], "depth_pro_photo.hip": ["-ffp-contract=off"],
             "point_cloud.hip": ["-ffp-contract=off"], "depth_eval.hip": ["-ffp-contract=off"],
             "depth_colorize.hip": ["-ffp-contract=off"], "preprocess_cubic.hip": ["-ffp-contract=off"],
-            "depth_quantiles.hip": ["-ffp-contract=off"], "cloud_view.hip": ["-ffp-contract=off"]}
+            "depth_quantiles.hip": ["-ffp-contract=off"], "cloud_view.hip": ["-ffp-contract=off"],
+            "depth_mesh.hip": ["-ffp-contract=off"]}
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
          "-Wno-unused-result", "-I", CSRC, "-I", INCLUDE]
 

@@ -176,6 +176,10 @@ PROTOTYPES = {
     "mde_op_point_cloud": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_float,
                            c_float, c_float, c_int, c_float, c_float, c_void_p, c_size_t, c_void_p, c_void_p,
                            c_size_t, c_void_p],
+    "mde_op_depth_mesh_ws_bytes": [c_int, c_int, c_int, c_int],
+    "mde_op_depth_mesh": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_float,
+                          c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_size_t, c_void_p,
+                          c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p],
     "mde_op_cloud_view_ws_bytes": [c_int, c_int, c_int, c_int, c_int, c_int],
     "mde_op_cloud_view": [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_float,
                           c_float, c_float, C.c_double, C.c_double, C.c_double, C.c_double, c_void_p, P(c_int),
@@ -200,6 +204,7 @@ PROTOTYPES = {
 }
 _RESTYPE = {"mde_last_error": c_char_p, "mde_op_attention_ws_bytes": c_size_t,
              "mde_op_point_cloud_ws_bytes": c_size_t, "mde_op_cloud_view_ws_bytes": c_size_t,
+             "mde_op_depth_mesh_ws_bytes": c_size_t,
              "mde_op_depth_eval_ws_bytes": c_size_t,
              "mde_op_depth_colorize_ws_bytes": c_size_t, "mde_op_depth_quantiles_ws_bytes": c_size_t}
 

@@ -222,6 +222,17 @@ size_t point_cloud_ws_bytes(int B, int h, int w, int step);
 hipError_t launch_point_cloud(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
                               int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
                               float z_lo, float z_hi, void* records, int* counts, void* ws, hipStream_t st);
+// depth_mesh.hip: the same grid, camera and vertex records as launch_point_cloud, after the depth-edge
+// filter (include/mde.h, mde_op_depth_mesh): the vertices the kept quads use (faces != 0) or the clean
+// samples (faces == 0), compacted, and two 13-byte PLY face entries per kept quad; vertex_counts, face_counts
+// int[B]; ws = depth_mesh_ws_bytes() of 4-byte aligned scratch.  Enqueues six kernels (four without
+// faces), nothing else.  No argument checks here: the ABI wrapper in ops_abi.hip holds the only copy of
+// the limits
+size_t depth_mesh_ws_bytes(int B, int h, int w, int step);
+hipError_t launch_depth_mesh(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
+                             int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, float z_lo,
+                             float z_hi, float edge_rtol, float edge_atol, int faces, void* vertices,
+                             int* vertex_counts, void* face_records, int* face_counts, void* ws, hipStream_t st);
 // depth_eval.hip: fp32 prediction and ground truth [B][h][w] and a uint8 mask -> double out[B][16]
 // (include/mde.h, mde_op_depth_eval: fit status and parameters, the metrics, the orientation);
 // ws = depth_eval_ws_bytes() of 8-byte aligned scratch.  Enqueues four kernels, nothing else.  No

@@ -156,6 +156,45 @@ int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, co
          "mde_op_point_cloud");
 }
 
+size_t mde_op_depth_mesh_ws_bytes(int batch, int h, int w, int step) {
+  long long plane = 0;
+  if (point_cloud_geometry_error(batch, h, w, step, &plane)) return 0;
+  return depth_mesh_ws_bytes(batch, h, w, step);
+}
+
+int mde_op_depth_mesh(const float* depth, int batch, int h, int w, int step, const unsigned char* photo, int pitch,
+                      int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, float z_lo,
+                      float z_hi, float edge_rtol, float edge_atol, int faces, void* vertices, size_t vertices_bytes,
+                      int* vertex_counts, void* face_records, size_t faces_bytes, int* face_counts, void* ws,
+                      size_t ws_bytes, void* st) {
+  long long plane = 0;
+  const char* why = (!depth || !vertices || !vertex_counts) ? "null pointer"
+                                                            : point_cloud_geometry_error(batch, h, w, step, &plane);
+  if (!why && photo && pitch < 3 * (long long)w) why = "pitch < 3 * w";
+  if (!why && !f_px_dev && !(fx > 0.f && fy > 0.f)) why = "f_px_dev is null and fx <= 0 or fy <= 0";
+  if (!why && !(cx == cx && cy == cy)) why = "cx or cy is NaN";
+  if (!why && vertices_bytes < (unsigned long long)batch * plane * (photo ? 15 : 12))
+    why = "vertices_bytes < batch * hs * ws * record size";
+  if (!why && !(z_lo <= z_hi)) why = "z_lo > z_hi (or NaN)";
+  if (!why && !(edge_rtol >= 0.f && edge_atol >= 0.f)) why = "edge_rtol or edge_atol is negative or NaN";
+  if (!why && faces) {
+    // triangles of one image: < 2 * plane, no overflow in 64 bits; batch <= 65535 and 13 bytes each neither
+    const long long tri = 2 * ((h + (long long)step - 1) / step - 1) * ((w + (long long)step - 1) / step - 1);
+    if (!face_records || !face_counts) why = "faces with a null face_records or face_counts";
+    else if (tri >= 0x7fffffffLL - 256) why = "faces: 2 * (hs - 1) * (ws - 1) of 2^31 - 256 or more";
+    else if (faces_bytes < (unsigned long long)batch * tri * 13)
+      why = "faces_bytes < batch * 2 * (hs - 1) * (ws - 1) * 13";
+  }
+  if (!why && (!ws || ws_bytes < depth_mesh_ws_bytes(batch, h, w, step)))
+    why = "needs ws of mde_op_depth_mesh_ws_bytes()";
+  if (!why && (reinterpret_cast<uintptr_t>(ws) & 3)) why = "ws must be 4-byte aligned";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_depth_mesh: ") + why);
+  OP_RET(launch_depth_mesh(depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy, z_lo, z_hi,
+                           edge_rtol, edge_atol, faces, vertices, vertex_counts, face_records, face_counts, ws,
+                           (hipStream_t)st),
+         "mde_op_depth_mesh");
+}
+
 namespace {
 // what mde_op_cloud_view_ws_bytes can judge: the point-cloud op's geometry, the picture, and the limits of
 // the selection (three planes per image on grid.y; an image's two planes pooled in one quantile call)

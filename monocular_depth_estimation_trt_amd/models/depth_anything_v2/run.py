@@ -12,7 +12,8 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
         [--source synthetic:vits:metric | ckpt.pth] [--input x.npy] [--src-hw H W]
         [--image photo.npy|photo.jpg] [--host-preprocess]
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
-        [--ply out.ply --f-px F [--ply-step N]]
+        [--ply out.ply --f-px F [--ply-step N] [--ply-edge-rtol R]]
+        [--mesh out.ply --f-px F [--mesh-step N] [--edge-rtol R] [--edge-atol A]]
         [--cloud-view out.png --f-px F [--cloud-view-size H W] [--cloud-view-angles ELEV AZIM] [--cloud-view-step N]]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
         [--color out.png [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near]]
@@ -41,6 +42,14 @@ driver's clamp [1e-3, 1e3] dropped.  There is no FOV head: `--f-px` (focal
 length in pixels at the source size) is required.  Relative models (the
 relative checkpoints, depth_anything_ac, distill_any_depth) are refused:
 relative depth is not turned into metres.
+
+`--mesh PATH` is the reference's models/metric_anything/demo_pointcloud.py:
+142-149 under the same conditions as `--ply`: samples on a depth edge (3x3
+spread of depth above `--edge-rtol`, default 0.1, times the depth, or above
+`--edge-atol`) are dropped, the surviving 2x2 blocks become two triangles each
+and the mesh is packed on the device (pointcloud.DeviceMesh) as a binary PLY
+with vertices and faces.  `--ply-edge-rtol R` gives `--ply`'s cloud the same
+edge filter, without faces.
 
 `--cloud-view PATH` draws that cloud instead of packing it: the reference's
 core/viz.py:render_points (demo.py:cloud_figure), an orthographic, z-buffered
@@ -76,7 +85,6 @@ import numpy as np
 
 from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, visualize, weights
 from monocular_depth_estimation_trt_amd import pointcloud
-from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
                                                            resize_linear_u8)
@@ -117,7 +125,8 @@ def build_parser(model="depth_anything_v2", mc=None):
                     help="write the point cloud (binary PLY; colours from --image) of the metric depth; needs --f-px")
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
     ap.add_argument("--f-px", type=float, default=None,
-                    help="with --ply / --cloud-view: focal length in pixels at the source size")
+                    help="with --ply / --mesh / --cloud-view: focal length in pixels at the source size")
+    pointcloud.add_mesh_arguments(ap)
     pointcloud.add_cloud_view_arguments(ap)
     evaluate.add_gt_arguments(ap)
     visualize.add_color_arguments(ap)
@@ -128,7 +137,7 @@ NOT_METRIC = "--ply needs a metric model: relative depth is not turned into metr
 
 
 def _check_ply(a, mc, opt="--ply"):
-    """--ply's (and --cloud-view's) conditions that can be answered before an engine is built."""
+    """--ply's (and --mesh's and --cloud-view's) conditions that can be answered before an engine is built."""
     if a.f_px is None or not a.f_px > 0:
         raise SystemExit(f"{opt} needs --f-px (a positive focal length in pixels): this model predicts none")
     if opt == "--ply" and a.ply_step < 1:
@@ -177,6 +186,9 @@ def main(argv=None, model="depth_anything_v2"):
         raise SystemExit("--host-preprocess needs --image")
     if a.ply:
         _check_ply(a, mc)
+    if a.mesh:
+        _check_ply(a, mc, "--mesh")
+    pointcloud.check_mesh_arguments(a)
     if a.cloud_view:
         _check_ply(a, mc, "--cloud-view")
         pointcloud.check_cloud_view_arguments(a)
@@ -189,6 +201,8 @@ def main(argv=None, model="depth_anything_v2"):
     gt_maps = evaluate.load_gt_arguments(a, gt_hw) if gt_policy else None
     if a.ply and img is not None and tuple(a.src_hw) != img.shape[:2]:
         raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
+    if a.mesh and img is not None and tuple(a.src_hw) != img.shape[:2]:
+        raise SystemExit("--mesh takes its colours from the --image photo: --src-hw must be the photo's size")
     if a.cloud_view and img is not None and tuple(a.src_hw) != img.shape[:2]:
         raise SystemExit("--cloud-view takes its colours from the --image photo: --src-hw must be the photo's size")
     if u8 and a.engine.endswith("_fp16.mdeng"):
@@ -214,6 +228,8 @@ def main(argv=None, model="depth_anything_v2"):
             engine.create_execution_context() as context:
         if a.ply and not engine.info.metric:
             raise SystemExit(NOT_METRIC)
+        if a.mesh and not engine.info.metric:
+            raise SystemExit(NOT_METRIC.replace("--ply", "--mesh"))
         if a.cloud_view and not engine.info.metric:
             raise SystemExit(NOT_METRIC.replace("--ply", "--cloud-view"))
         inputs, outputs, bindings, stream = allocate_buffers(engine, output_shape, profile_idx=0)
@@ -240,10 +256,13 @@ def main(argv=None, model="depth_anything_v2"):
             with DevicePostprocess(1, input_h, input_w, *a.src_hw) as pp:
                 depth = pp.run(outputs[0].device, stream)[0].copy()
                 if a.ply:  # the clamped map is still in pp.mem.device
-                    ms, n = device_ply(a.ply, pp.mem.device, *a.src_hw, stream, step=a.ply_step, img_bgr=img,
-                                       f_px=a.f_px, z_lo=1e-3, z_hi=1e3)
+                    ms, n = pointcloud.driver_ply(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px,
+                                                  z_lo=1e-3, z_hi=1e3)
                     print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {a.src_hw[0]}x{a.src_hw[1]} step "
                           f"{a.ply_step} -> {a.ply} : {ms:0.3f} ms, {n} points")
+                if a.mesh:
+                    pointcloud.driver_mesh(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px, z_lo=1e-3,
+                                           z_hi=1e3)
                 if a.cloud_view:
                     pointcloud.driver_cloud_view(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px)
                 if gt_policy:

@@ -11,7 +11,8 @@
     python -m monocular_depth_estimation_trt_amd.models.depth_pro.run \
         [--source synthetic:depth_pro | DepthPro.safetensors] [--image photo.npy|photo.jpg]
         [--input x.npy] [--src-hw H W] [--f-px F] [--host-preprocess] [--host-postprocess]
-        [--ply out.ply] [--ply-step N]
+        [--ply out.ply] [--ply-step N] [--ply-edge-rtol R]
+        [--mesh out.ply [--mesh-step N] [--edge-rtol R] [--edge-atol A]]
         [--cloud-view out.png [--cloud-view-size H W] [--cloud-view-angles ELEV AZIM] [--cloud-view-step N]]
         [--gt depth.npy --gt-mask mask.npy [--max-depth M] [--gt-out PATH.json]]
         [--color out.png [--color-range VMIN VMAX | --color-robust [LO HI]] [--color-robust-near]]
@@ -38,6 +39,15 @@ photo (no colours with `--input` or the synthetic image).  It runs on the
 device (pointcloud.DevicePointCloud) on the depth map and the focal length the
 device post-process left there, drops depths outside [1e-4, 1e4] and downloads
 the PLY records; `--ply-step N` keeps every N-th pixel on both axes.
+
+`--mesh PATH` is the reference's `models/metric_anything/demo_pointcloud.py:
+142-149`: the samples on a depth edge -- a 3x3 spread of depth above
+`--edge-rtol` (default 0.1, the reference's) times the depth, or above
+`--edge-atol` metres -- are dropped, the 2x2 blocks that survive whole become
+two triangles each, and the vertices they use and the faces are packed on the
+device (pointcloud.DeviceMesh, `mde_op_depth_mesh`) and written as a binary PLY
+with `element vertex` and `element face`.  `--ply-edge-rtol R` gives `--ply`'s
+cloud the same edge filter (no flying pixels), without faces.
 
 `--cloud-view PATH` is the reference's `core/viz.py:render_points` (what
 `demo.py:cloud_figure` shows): an orthographic, z-buffered picture of that
@@ -75,7 +85,6 @@ from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, vi
 from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
                                                                stream_synchronize)
 from monocular_depth_estimation_trt_amd import pointcloud
-from monocular_depth_estimation_trt_amd.pointcloud import device_ply
 from monocular_depth_estimation_trt_amd.postprocess import DepthProDevicePostprocess, depth_pro_postprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DepthProPreprocess, load_image_bgr,
                                                            preprocess_depth_pro_host)
@@ -112,6 +121,7 @@ def build_parser(model="depth_pro", size=None):
     ap.add_argument("--ply", default="", metavar="PATH",
                     help="write the point cloud (binary PLY; colours from --image) of the metric depth")
     ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
+    pointcloud.add_mesh_arguments(ap)
     pointcloud.add_cloud_view_arguments(ap)
     evaluate.add_gt_arguments(ap)
     visualize.add_color_arguments(ap)
@@ -162,12 +172,15 @@ def _device_preprocess(img, size, mem, stream):
         ev.free()
 
 
-def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None, color=None, cloud_view=None):
+def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None, color=None, cloud_view=None,
+                        mesh=None):
     """DepthProDevicePostprocess on the output bindings in place, timed with
     hipEvents (kernel + D2H of the depth map and the focal length); `ply` =
-    (path, step, photo or None): then the point cloud of the map, while it is
-    still on the device, with the focal length the post-process used (the
-    fourth result, pointcloud.device_ply's; else None); `score`: called with
+    (the parsed arguments, photo or None): then the point cloud of the map,
+    while it is still on the device, with the focal length the post-process
+    used (the fourth result, pointcloud.driver_ply's; else None); `mesh`:
+    called with the map's and the focal length's device pointers (--mesh);
+    `score`: called with
     the map's device pointer while it is still there (--gt); `color`: likewise
     (--color); `cloud_view`: likewise, with the device focal length as well
     (--cloud-view)."""
@@ -184,9 +197,11 @@ def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=Non
             depth, f, ms = depth[0].copy(), float(f[0]), ev.ms()
             cloud = None
             if ply:
-                path, step, img = ply
-                cloud = device_ply(path, pp.mem.device, *src_hw, stream, step=step, img_bgr=img,
-                                   d_f_px=pp.f_px.device, f_px=f_px, z_lo=1e-4, z_hi=1e4)
+                a, img = ply
+                cloud = pointcloud.driver_ply(a, pp.mem.device, src_hw, stream, img_bgr=img, d_f_px=pp.f_px.device,
+                                              f_px=f_px, z_lo=1e-4, z_hi=1e4)
+            if mesh:
+                mesh(pp.mem.device, pp.f_px.device)
             if score:
                 score(pp.mem.device)
             if color:
@@ -213,6 +228,10 @@ def main(argv=None, model="depth_pro"):
                          "--host-postprocess")
     if a.ply and a.ply_step < 1:
         raise SystemExit("--ply-step must be positive")
+    if a.mesh and a.host_postprocess:
+        raise SystemExit("--mesh runs on the device post-process's depth map: do not combine it with "
+                         "--host-postprocess")
+    pointcloud.check_mesh_arguments(a)
     if a.cloud_view and a.host_postprocess:
         raise SystemExit("--cloud-view runs on the device post-process's depth map: do not combine it with "
                          "--host-postprocess")
@@ -239,6 +258,8 @@ def main(argv=None, model="depth_pro"):
     gt_maps = evaluate.load_gt_arguments(a, src_hw) if gt_policy else None
     if a.ply and img is not None and src_hw != img.shape[:2]:
         raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
+    if a.mesh and img is not None and src_hw != img.shape[:2]:
+        raise SystemExit("--mesh takes its colours from the --image photo: --src-hw must be the photo's size")
     if a.cloud_view and img is not None and src_hw != img.shape[:2]:
         raise SystemExit("--cloud-view takes its colours from the --image photo: --src-hw must be the photo's size")
     output_shapes = (1, 1, size, size)
@@ -267,9 +288,11 @@ def main(argv=None, model="depth_pro"):
             color = (lambda d_map: visualize.driver_color(a, s, d_map, src_hw, stream)) if a.color else None
             view = (lambda d_map, d_f: pointcloud.driver_cloud_view(a, d_map, src_hw, stream, img_bgr=img, d_f_px=d_f,
                                                                     f_px=a.f_px)) if a.cloud_view else None
+            mesh = (lambda d_map, d_f: pointcloud.driver_mesh(a, d_map, src_hw, stream, img_bgr=img, d_f_px=d_f,
+                                                              f_px=a.f_px, z_lo=1e-4, z_hi=1e4)) if a.mesh else None
             depth, f_px, ms, cloud = _device_postprocess(outputs, size, src_hw, a.f_px, stream,
-                                                         ply=(a.ply, a.ply_step, img) if a.ply else None, score=score,
-                                                         color=color, cloud_view=view)
+                                                         ply=(a, img) if a.ply else None, score=score,
+                                                         color=color, cloud_view=view, mesh=mesh)
             print(f"[MDET] postprocess (device, kernel + D2H, hipEvents) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{ms:0.3f} ms")
             if cloud:

@@ -18,6 +18,14 @@ depth map without the records leaving the device.  `render_np` restates its
 contract in numpy (the kernels are held to it, the picture byte for byte and
 the view row bit for bit), `DeviceCloudView` owns the buffers and drives the
 op, `device_cloud_view` is what the drivers' `--cloud-view` calls.
+
+The mesh of that cloud -- the reference's `models/metric_anything/
+demo_pointcloud.py:142-149`: depth edges (flying pixels) dropped, two triangles
+per surviving 2 x 2 block, no unreferenced vertices -- is `mde_op_depth_mesh`
+(csrc/depth_mesh.hip).  `mesh_np` restates its contract in numpy float32 (the
+kernels are held to it byte for byte), `DeviceMesh` owns the buffers and
+drives the op, `write_ply_mesh` / `read_ply_mesh` handle the vertex + face
+PLY, `device_mesh` is what the drivers' `--mesh` and `--ply-edge-rtol` call.
 """
 
 from __future__ import annotations
@@ -588,6 +596,366 @@ def read_ply(path) -> np.ndarray:
     raise ValueError(f"{path}: the header is not one write_ply writes")
 
 
+# ---- meshes: mde_op_depth_mesh (csrc/depth_mesh.hip) ---------------------------------------------------
+# The reference's models/metric_anything/demo_pointcloud.py:142-149 -- depth edges dropped, a triangle
+# mesh over what is left, no unreferenced vertices.  mesh_np restates the include/mde.h contract.
+
+FACE_DTYPE = np.dtype([("n", "u1"), ("i0", "<i4"), ("i1", "<i4"), ("i2", "<i4")])  # 13 bytes, a PLY list entry
+# the flag byte of a sample (csrc/depth_mesh.hip writes the same byte into its scratch)
+F_VALID, F_EDGE, F_CLEAN, F_QUAD, F_DIAG_BD, F_VERTEX = 1, 2, 4, 8, 16, 32
+EDGE_RTOL = 0.1          # demo_pointcloud.py:143
+
+
+def _max3x3(a: np.ndarray) -> np.ndarray:
+    """Maximum over the 3 x 3 neighbourhood clipped to the array (-inf outside)."""
+    p = np.full((a.shape[0] + 2, a.shape[1] + 2), -np.inf, a.dtype)
+    p[1:-1, 1:-1] = a
+    out = a.copy()
+    for di in range(3):
+        for dj in range(3):
+            np.maximum(out, p[di:di + a.shape[0], dj:dj + a.shape[1]], out=out)
+    return out
+
+
+def mesh_np(depth, fx, fy, cx, cy, photo=None, swap_rb=False, step=1, z_lo=1e-4, z_hi=1e4, edge_rtol=EDGE_RTOL,
+            edge_atol=0.0, faces=True):
+    """The include/mde.h contract of mde_op_depth_mesh for one image, in numpy
+    float32 with one rounding per operation, on the sampled grid of
+    `unproject_np`:
+
+        valid = z == z and z_lo <= z <= z_hi
+        diff  = zmax - zmin over the valid samples of the clipped 3 x 3 window
+        edge  = valid and ((atol > 0 and diff > atol) or (rtol > 0 and diff / z > rtol))
+        clean = valid and not edge
+        quad (i, j) kept iff a = (i, j), b = (i, j + 1), c = (i + 1, j + 1), d = (i + 1, j) are clean;
+        |za - zc| <= |zb - zd|: triangles (a, d, c), (a, c, b), else (a, d, b), (b, d, c)
+        vertex = one of its quads is kept (faces) / clean (not faces)
+
+    Returns (vertex records, 1-D `vertex_dtype`, row-major; face records, 1-D
+    FACE_DTYPE, row-major by quad, empty without `faces`; flags uint8 [hs, ws],
+    the F_* bits)."""
+    f32 = np.float32
+    zfull = np.asarray(depth, dtype=np.float32)
+    rtol, atol = f32(edge_rtol), f32(edge_atol)
+    if not (rtol >= 0 and atol >= 0):
+        raise ValueError("edge_rtol and edge_atol must not be negative or NaN")
+    rec = unproject_np(zfull, fx, fy, cx, cy, photo=photo, swap_rb=swap_rb, step=step)
+    z = zfull[::step, ::step]
+    hs, ws = z.shape
+    with np.errstate(all="ignore"):
+        valid = (z == z) & (z >= f32(z_lo)) & (z <= f32(z_hi))
+        zmax = _max3x3(np.where(valid, z, f32(-np.inf)))
+        zmin = -_max3x3(np.where(valid, -z, f32(-np.inf)))
+        diff = zmax - zmin
+        ratio = diff / z
+        assert diff.dtype == ratio.dtype == np.float32
+        edge = valid & (((atol > 0) & (diff > atol)) | ((rtol > 0) & (ratio > rtol)))
+        clean = valid & ~edge
+        quad = np.zeros((hs, ws), bool)
+        bd = np.zeros((hs, ws), bool)
+        if hs > 1 and ws > 1:
+            quad[:-1, :-1] = clean[:-1, :-1] & clean[:-1, 1:] & clean[1:, 1:] & clean[1:, :-1]
+            bd[:-1, :-1] = quad[:-1, :-1] & ~(np.abs(z[:-1, :-1] - z[1:, 1:]) <= np.abs(z[:-1, 1:] - z[1:, :-1]))
+    if faces:
+        vertex = quad.copy()
+        vertex[:, 1:] |= quad[:, :-1]
+        vertex[1:, :] |= quad[:-1, :]
+        vertex[1:, 1:] |= quad[:-1, :-1]
+    else:
+        vertex = clean
+    flags = (valid * F_VALID + edge * F_EDGE + clean * F_CLEAN + quad * F_QUAD + bd * F_DIAG_BD
+             + vertex * F_VERTEX).astype(np.uint8)
+    index = (np.cumsum(vertex.reshape(-1), dtype=np.int64) - 1).reshape(hs, ws)
+    tri = np.zeros((0, 2), FACE_DTYPE)
+    if faces and quad.any():
+        qi, qj = np.nonzero(quad)  # row-major
+        a, b, c, d = index[qi, qj], index[qi, qj + 1], index[qi + 1, qj + 1], index[qi + 1, qj]
+        split = bd[qi, qj]
+        tri = np.empty((qi.size, 2), FACE_DTYPE)
+        tri["n"] = 3
+        tri["i0"][:, 0], tri["i1"][:, 0], tri["i2"][:, 0] = a, d, np.where(split, b, c)
+        tri["i0"][:, 1], tri["i1"][:, 1], tri["i2"][:, 1] = np.where(split, b, a), np.where(split, d, c), \
+            np.where(split, c, b)
+    return rec[vertex.reshape(-1)], tri.reshape(-1), flags
+
+
+def mesh_ws_bytes(batch: int, h: int, w: int, step: int = 1) -> int:
+    """Device scratch mde_op_depth_mesh needs (mde_op_depth_mesh_ws_bytes); 0: refused."""
+    return int(_lib.lib().mde_op_depth_mesh_ws_bytes(int(batch), int(h), int(w), int(step)))
+
+
+def depth_mesh(d_depth: int, batch: int, h: int, w: int, step: int, d_photo: int, pitch: int, swap_rb: bool,
+               d_f_px: int, fx: float, fy: float, cx: float, cy: float, z_lo: float, z_hi: float, edge_rtol: float,
+               edge_atol: float, faces: bool, d_vertices: int, vertices_bytes: int, d_vertex_counts: int, d_faces: int,
+               faces_bytes: int, d_face_counts: int, d_ws: int, ws_nbytes: int, stream: int = 0) -> None:
+    """Device pointers in/out, enqueued on `stream` (mde_op_depth_mesh)."""
+    _lib.call("mde_op_depth_mesh", C.c_void_p(int(d_depth)), int(batch), int(h), int(w), int(step),
+              C.c_void_p(int(d_photo or 0)), int(pitch), int(bool(swap_rb)), C.c_void_p(int(d_f_px or 0)),
+              float(fx), float(fy), float(cx), float(cy), float(z_lo), float(z_hi), float(edge_rtol),
+              float(edge_atol), int(bool(faces)), C.c_void_p(int(d_vertices)), int(vertices_bytes),
+              C.c_void_p(int(d_vertex_counts)), C.c_void_p(int(d_faces or 0)), int(faces_bytes),
+              C.c_void_p(int(d_face_counts or 0)), C.c_void_p(int(d_ws or 0)), int(ws_nbytes),
+              C.c_void_p(int(stream or 0)))
+
+
+class DeviceMesh:
+    """Owns the vertex and face records and the two counts (device + pinned
+    host) and the scratch of mde_op_depth_mesh for `batch` depth maps [h, w],
+    with or without colour, sampling every `step`-th pixel; `faces` off: the
+    edge-filtered cloud only, no face buffers.
+
+    enqueue(d_depth, stream, ...) only enqueues the kernels (capturable);
+    download(stream) brings both counts back, synchronizes once, then copies
+    only the counted bytes of each image's regions and synchronizes again;
+    result() is one (`vertex_dtype` view, FACE_DTYPE view) pair per image,
+    valid until the next download; run() = enqueue, download, result."""
+
+    def __init__(self, batch: int, h: int, w: int, colour: bool, step: int = 1, faces: bool = True):
+        self.batch, self.h, self.w, self.step = int(batch), int(h), int(w), int(step)
+        self.colour, self.faces = bool(colour), bool(faces)
+        self.hs, self.ws = grid(self.h, self.w, self.step)
+        self.dtype = vertex_dtype(self.colour)
+        self.region = self.hs * self.ws * self.dtype.itemsize                       # vertex bytes per image
+        self.face_region = 2 * (self.hs - 1) * (self.ws - 1) * FACE_DTYPE.itemsize  # face bytes per image
+        self.vertices: Optional[HostDeviceMem] = None
+        self.face_records: Optional[HostDeviceMem] = None
+        self.counts: Optional[HostDeviceMem] = None  # [2][batch]: vertices, triangles
+        self._ws = 0
+        self._ws_bytes = mesh_ws_bytes(self.batch, self.h, self.w, self.step)
+        if self._ws_bytes == 0:
+            raise ValueError(f"mde_op_depth_mesh does not take batch {batch}, {h}x{w}, step {step}")
+        try:
+            self.vertices = HostDeviceMem(self.batch * self.region, np.uint8)
+            if self.faces:  # at least one byte: the op wants a pointer even where no quad exists
+                self.face_records = HostDeviceMem(max(self.batch * self.face_region, 1), np.uint8)
+            self.counts = HostDeviceMem(2 * self.batch, np.dtype(np.int32))
+            p = C.c_void_p()
+            _lib.call("mde_rt_malloc", C.byref(p), self._ws_bytes)
+            self._ws = int(p.value)
+        except Exception:
+            self.free()
+            raise
+
+    def enqueue(self, d_depth: int, stream: int, d_photo: int = 0, pitch: int = 0, swap_rb: bool = False,
+                d_f_px: int = 0, fx: Optional[float] = None, fy: Optional[float] = None,
+                cx: Optional[float] = None, cy: Optional[float] = None, z_lo: float = 1e-4, z_hi: float = 1e4,
+                edge_rtol: float = EDGE_RTOL, edge_atol: float = 0.0) -> None:
+        """The kernels on `stream`, nothing else.  Focal lengths and cx, cy as
+        for DevicePointCloud.enqueue."""
+        if self.vertices is None:
+            raise RuntimeError("DeviceMesh already freed")
+        if bool(d_photo) != self.colour:
+            raise ValueError("DeviceMesh(colour=%s) %s a photo" % (self.colour, "needs" if self.colour else
+                                                                   "does not take"))
+        if not d_f_px and fx is None:
+            raise ValueError("DeviceMesh.enqueue needs d_f_px or fx")
+        fx = 0.0 if fx is None else float(fx)
+        fy = fx if fy is None else float(fy)
+        depth_mesh(d_depth, self.batch, self.h, self.w, self.step, d_photo, pitch or 3 * self.w, swap_rb, d_f_px, fx,
+                   fy, self.w / 2 if cx is None else cx, self.h / 2 if cy is None else cy, z_lo, z_hi, edge_rtol,
+                   edge_atol, self.faces, self.vertices.device, self.batch * self.region, self.counts.device,
+                   self.face_records.device if self.faces else 0, self.batch * self.face_region if self.faces else 0,
+                   self.counts.device + 4 * self.batch if self.faces else 0, self._ws, self._ws_bytes, stream)
+
+    def download(self, stream: int) -> None:
+        """Both counts first, then only the counted bytes; synchronizes `stream` twice."""
+        if self.vertices is None:
+            raise RuntimeError("DeviceMesh already freed")
+        s = C.c_void_p(int(stream or 0))
+        if not self.faces:
+            self.counts.host[self.batch:] = 0
+        _lib.call("mde_rt_memcpy_dtoh_async", self.counts.host.ctypes.data_as(C.c_void_p),
+                  C.c_void_p(self.counts.device), self.counts.nbytes if self.faces else 4 * self.batch, s)
+        stream_synchronize(stream)
+        for b in range(self.batch):
+            for mem, region, n in ((self.vertices, self.region, int(self.counts.host[b]) * self.dtype.itemsize),
+                                   (self.face_records, self.face_region,
+                                    int(self.counts.host[self.batch + b]) * FACE_DTYPE.itemsize)):
+                if n:
+                    _lib.call("mde_rt_memcpy_dtoh_async", C.c_void_p(mem.host.ctypes.data + b * region),
+                              C.c_void_p(mem.device + b * region), n, s)
+        stream_synchronize(stream)
+
+    def result(self):
+        """One (vertices, faces) pair of views per image; valid after download()."""
+        if self.vertices is None:
+            raise RuntimeError("DeviceMesh already freed")
+        out = []
+        for b in range(self.batch):
+            nv, nf = int(self.counts.host[b]), int(self.counts.host[self.batch + b])
+            v = self.vertices.host[b * self.region:b * self.region + nv * self.dtype.itemsize].view(self.dtype)
+            f = (self.face_records.host[b * self.face_region:b * self.face_region + nf * FACE_DTYPE.itemsize]
+                 .view(FACE_DTYPE) if self.faces else np.zeros(0, FACE_DTYPE))
+            out.append((v, f))
+        return out
+
+    def run(self, d_depth: int, stream: int, **kw):
+        self.enqueue(d_depth, stream, **kw)
+        self.download(stream)
+        return self.result()
+
+    def free(self) -> None:
+        for m in (self.vertices, self.face_records, self.counts):
+            if m is not None:
+                m.free()
+        self.vertices = self.face_records = self.counts = None
+        if self._ws:
+            _lib.call("mde_rt_free", C.c_void_p(self._ws))
+            self._ws = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+def mesh_header(vertex_count: int, face_count: int, colour: bool) -> bytes:
+    lines = ply_header(vertex_count, colour).decode("ascii").split("\n")[:-2]  # without end_header
+    lines += [f"element face {int(face_count)}", "property list uchar int vertex_indices"]
+    return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
+
+
+def write_ply_mesh(path, vertices: np.ndarray, faces: np.ndarray) -> None:
+    """The ASCII header with `element vertex` and `element face`, then the
+    bytes of `vertices` (1-D `vertex_dtype`) and of `faces` (1-D FACE_DTYPE) as
+    they are -- as they came off the card."""
+    vertices, faces = np.asarray(vertices), np.asarray(faces)
+    colour = vertices.dtype == vertex_dtype(True)
+    if vertices.ndim != 1 or not (colour or vertices.dtype == vertex_dtype(False)):
+        raise ValueError(f"write_ply_mesh wants a 1-D vertex_dtype array, got {vertices.dtype} {vertices.shape}")
+    if faces.ndim != 1 or faces.dtype != FACE_DTYPE:
+        raise ValueError(f"write_ply_mesh wants a 1-D FACE_DTYPE array, got {faces.dtype} {faces.shape}")
+    with open(path, "wb") as f:
+        f.write(mesh_header(vertices.shape[0], faces.shape[0], colour))
+        f.write(np.ascontiguousarray(vertices).tobytes())
+        f.write(np.ascontiguousarray(faces).tobytes())
+
+
+def read_ply_mesh(path):
+    """Read a file of exactly write_ply_mesh's form back: (vertices, faces)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: no PLY header")
+    body = end + len(b"end_header\n")
+    counts = {}
+    for line in data[:body].decode("ascii", errors="replace").split("\n"):
+        part = line.split(" ")
+        if len(part) == 3 and part[0] == "element" and part[2].isdigit():
+            counts[part[1]] = int(part[2])
+    if set(counts) != {"vertex", "face"}:
+        raise ValueError(f"{path}: not a vertex + face PLY header")
+    for colour in (True, False):
+        if data[:body] == mesh_header(counts["vertex"], counts["face"], colour):
+            dt = vertex_dtype(colour)
+            nv, nf = counts["vertex"] * dt.itemsize, counts["face"] * FACE_DTYPE.itemsize
+            if len(data) - body != nv + nf:
+                raise ValueError(f"{path}: {len(data) - body} body bytes, the header promises {nv + nf}")
+            faces = np.frombuffer(data, dtype=FACE_DTYPE, count=counts["face"], offset=body + nv).copy()
+            if (faces["n"] != 3).any():
+                raise ValueError(f"{path}: a face that is not a triangle")
+            return np.frombuffer(data, dtype=dt, count=counts["vertex"], offset=body).copy(), faces
+    raise ValueError(f"{path}: the header is not one write_ply_mesh writes")
+
+
+def device_mesh(path, d_depth: int, h: int, w: int, stream: int, step: int = 1, img_bgr: Optional[np.ndarray] = None,
+                d_f_px: int = 0, f_px: Optional[float] = None, z_lo: float = 1e-4, z_hi: float = 1e4,
+                edge_rtol: float = EDGE_RTOL, edge_atol: float = 0.0, faces: bool = True):
+    """What the model drivers' --mesh does (and, with `faces` off, --ply with
+    --ply-edge-rtol): DeviceMesh on one device depth map [h][w] at `d_depth`,
+    camera and colours as for `device_ply`, written to `path` (a mesh PLY, or
+    with `faces` off write_ply's vertex-only file).  Returns (ms of the kernels
+    + D2H between two hipEvents on `stream`, vertices, triangles)."""
+    if img_bgr is not None and (img_bgr.dtype != np.uint8 or img_bgr.shape != (h, w, 3)):
+        raise ValueError(f"the photo must be uint8 [{h}, {w}, 3], got {img_bgr.dtype} {img_bgr.shape}")
+    s = C.c_void_p(int(stream or 0))
+    photo = None
+    ev = [C.c_void_p(), C.c_void_p()]
+    try:
+        for e in ev:
+            _lib.call("mde_rt_event_create", C.byref(e))
+        if img_bgr is not None:
+            photo = HostDeviceMem(h * w * 3, np.uint8)
+            photo.host = np.ascontiguousarray(img_bgr).reshape(-1)
+            _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(photo.device), photo.host.ctypes.data_as(C.c_void_p),
+                      photo.nbytes, s)
+        with DeviceMesh(1, h, w, colour=photo is not None, step=step, faces=faces) as mesh:
+            _lib.call("mde_rt_event_record", ev[0], s)
+            mesh.enqueue(d_depth, stream, d_photo=photo.device if photo else 0, pitch=3 * w, swap_rb=True,
+                         d_f_px=0 if f_px is not None else d_f_px, fx=f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=edge_rtol,
+                         edge_atol=edge_atol)
+            mesh.download(stream)
+            _lib.call("mde_rt_event_record", ev[1], s)
+            stream_synchronize(stream)
+            vertices, tri = mesh.result()[0]
+            if faces:
+                write_ply_mesh(path, vertices, tri)
+            else:
+                write_ply(path, vertices)
+            ms = C.c_float()
+            _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
+            return float(ms.value), int(vertices.shape[0]), int(tri.shape[0])
+    finally:
+        if photo is not None:
+            photo.free()
+        for e in ev:
+            if e:
+                _lib.call("mde_rt_event_destroy", e)
+
+
+def add_mesh_arguments(ap) -> None:
+    """The drivers' --mesh options and --ply's edge filter."""
+    ap.add_argument("--mesh", default="", metavar="PATH",
+                    help="write a triangle mesh (binary PLY; colours from --image) of the metric depth without its "
+                         "depth edges")
+    ap.add_argument("--mesh-step", type=int, default=1, help="with --mesh: keep every N-th pixel on both axes")
+    ap.add_argument("--edge-rtol", type=float, default=EDGE_RTOL,
+                    help="with --mesh: a sample whose 3x3 depth spread / depth exceeds this is an edge (0: off)")
+    ap.add_argument("--edge-atol", type=float, default=0.0,
+                    help="with --mesh: a sample whose 3x3 depth spread exceeds this is an edge (0: off)")
+    ap.add_argument("--ply-edge-rtol", type=float, default=None, metavar="R",
+                    help="with --ply: drop depth edges (flying pixels) from the cloud, as --edge-rtol does for --mesh")
+
+
+def check_mesh_arguments(a) -> None:
+    """The conditions of --mesh and --ply-edge-rtol that need no engine."""
+    if a.mesh:
+        if a.mesh_step < 1:
+            raise SystemExit("--mesh-step must be positive")
+        if not (a.edge_rtol >= 0 and a.edge_atol >= 0):
+            raise SystemExit("--edge-rtol and --edge-atol must not be negative")
+    if a.ply_edge_rtol is not None:
+        if not a.ply:
+            raise SystemExit("--ply-edge-rtol needs --ply")
+        if not a.ply_edge_rtol >= 0:
+            raise SystemExit("--ply-edge-rtol must not be negative")
+
+
+def driver_mesh(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, z_lo=1e-4, z_hi=1e4):
+    """The drivers' --mesh: the mesh of the device map [hw] at `d_depth` and
+    its `[MDET] mesh ...` line.  Returns (vertices, triangles)."""
+    ms, nv, nf = device_mesh(a.mesh, d_depth, hw[0], hw[1], stream, step=a.mesh_step, img_bgr=img_bgr, d_f_px=d_f_px,
+                             f_px=f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=a.edge_rtol, edge_atol=a.edge_atol)
+    print(f"[MDET] mesh (device, kernels + D2H, hipEvents) {hw[0]}x{hw[1]} step {a.mesh_step} rtol {a.edge_rtol:g} "
+          f"atol {a.edge_atol:g} -> {a.mesh} : {ms:0.3f} ms, {nv} vertices, {nf} triangles")
+    return nv, nf
+
+
+def driver_ply(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, z_lo=1e-4, z_hi=1e4):
+    """The drivers' --ply: `device_ply`, or with --ply-edge-rtol the
+    edge-filtered cloud of `device_mesh`; (ms, points)."""
+    if a.ply_edge_rtol is None:
+        return device_ply(a.ply, d_depth, hw[0], hw[1], stream, step=a.ply_step, img_bgr=img_bgr, d_f_px=d_f_px,
+                          f_px=f_px, z_lo=z_lo, z_hi=z_hi)
+    return device_mesh(a.ply, d_depth, hw[0], hw[1], stream, step=a.ply_step, img_bgr=img_bgr, d_f_px=d_f_px,
+                       f_px=f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=a.ply_edge_rtol, faces=False)[:2]
+
+
 __all__ = ["vertex_dtype", "grid", "unproject_np", "ws_bytes", "point_cloud", "DevicePointCloud", "device_ply", "ply_header",
            "write_ply", "read_ply", "view_trig", "render_np", "cloud_view_ws_bytes", "cloud_view", "DeviceCloudView",
-           "device_cloud_view", "add_cloud_view_arguments", "check_cloud_view_arguments", "driver_cloud_view"]
+           "device_cloud_view", "add_cloud_view_arguments", "check_cloud_view_arguments", "driver_cloud_view",
+           "FACE_DTYPE", "mesh_np", "mesh_ws_bytes", "depth_mesh", "DeviceMesh", "mesh_header", "write_ply_mesh",
+           "read_ply_mesh", "device_mesh", "add_mesh_arguments", "check_mesh_arguments", "driver_mesh", "driver_ply"]
