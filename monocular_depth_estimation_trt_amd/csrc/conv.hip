@@ -48,6 +48,8 @@ namespace mde {
 namespace {
 
 __device__ __attribute__((aligned(64))) f16 g_zero_conv[64];
+// target of the persistent conv's row stores outside the map (a fixed number of stores per wave: its counted wait)
+__device__ __attribute__((aligned(16))) f16x8 g_sink_conv[64];
 
 typedef f16 f16x2c __attribute__((ext_vector_type(2)));
 
@@ -391,7 +393,8 @@ hipError_t conv_tiles(const GemmParams& p, hipStream_t st) {
 // immediate offset -- the tile loop is unrolled by two so the patch buffer
 // is a constant too (computed addresses cost ~3 VALU per MFMA, which the
 // 8 issue cycles an MFMA leaves cannot hold).  The input ReLU (conv1) is one
-// LDS pass over each landed patch, not 4 VALU per fragment read.
+// LDS pass over each landed patch (every wave over the rows its own DMAs
+// brought), not 4 VALU per fragment read.
 // MODE (the two RCU convs): 0 = ReLU'd input, bias, ReLU, no residual
 // (conv1); 1 = bias + res0; 2 = bias + res0 + res1 (conv2); 3 = plain (bias
 // optional: layer1_rn, whose 48 input channels are padded to 64).  Its own
@@ -405,7 +408,16 @@ hipError_t conv_tiles(const GemmParams& p, hipStream_t st) {
 // TYP = 16 (the default, switch value 1): 16 x 16-pixel tiles on 8 waves,
 // LDS 154 KB; 8 (value 2, A/B): 8 x 16 on 4 waves, 118 KB -- one wave per
 // SIMD, measured slower.  Each wave: 2 tile rows x 64 channels.
-template <int TYP, int MODE>
+// FOLD (MODE 1, switch "outconv_fold"): the 1x1 conv that follows (the fusion
+// block's out_conv, GemmParams::pw_*) runs on the tile before it leaves -- its
+// 64 x 64 weights sit in 32 registers per lane as MFMA operand fragments for
+// the whole run (LDS has 6 KB free); the wave parks its 32 finished f16 pixel
+// rows (bias, residual, one rounding: the values out16 would have held) in its
+// staging slice, reads them back as B fragments, runs the 16 MFMAs in the
+// GEMM's order (k-substep 0, then 1, one accumulator chain per output), adds
+// the 1x1's bias, rounds once and stores whole rows to pw_out.  out16 is not
+// written.  Bit-identical to conv + gemm_kernel.
+template <int TYP, int MODE, bool FOLD = false>
 __global__ void __launch_bounds__(TYP * 32) __attribute__((amdgpu_waves_per_eu(1)))
 conv64p_kernel(const GemmParams p) {
   constexpr int NW = TYP / 2, NT = NW * 64, TM = 2, TN = 4;
@@ -418,6 +430,7 @@ conv64p_kernel(const GemmParams p) {
   constexpr int EPIW = 16 * 64 * 4;  // staging slice per wave: 16 fp32 rows (or 32 f16 rows)
   constexpr int NRES = MODE == 3 ? 0 : MODE;
   constexpr bool F16STAGE = MODE == 0 || MODE == 3;  // no residual: the staged f16 value is the output
+  static_assert(!FOLD || MODE == 1, "the folded 1x1: bias + res0 only");
   static_assert(NW * EPIW <= PATCH, "epilogue staging fits the consumed patch buffer");
   static_assert(PATCH + ((TM + 1) * PW + 2) * ROWB < 65536 && 7 * 8192 + 3 * 2048 < 65536, "ds_read immediate offsets");
   static_assert(PW % 8 == 2, "pixel row stride = 2 mod 8 (the swizzle table below)");
@@ -447,22 +460,45 @@ conv64p_kernel(const GemmParams p) {
   }
   // ASM: the in-loop prefetch (glds16_asm); the prologue's patch uses the
   // builtin, drained by __syncthreads()'s vmcnt(0) before the loop
-  auto load_patch = [&](int tt, int buf, auto asm_tag) {
+  // A lane's pixel (py, px) within the patch in row group q = wave + k NW, and
+  // its byte offset from the patch's first pixel, do not depend on the tile:
+  // computed once, so that one DMA issue is two range checks, a select and a
+  // 64-bit add in straight-line code (per tile and group, the division by PW,
+  // the 64-bit pixel offset, two divergent branches and a scalar load of the
+  // zero line's address were ~35 instructions in front of the MFMAs).
+  // pyx: py | px << 16; rows past the patch (pp >= PHW) get a py outside any
+  // map (conv64p_mode: ch, cw < 32768)
+  constexpr int NQ = (PINS + NW - 1) / NW;
+  int prel[NQ], pyx[NQ];
+#pragma unroll
+  for (int k = 0; k < NQ; ++k) {
+    const int pp = (wave + k * NW) * RWP + lrow;
+    const int py = pp / PW, px = pp - (pp / PW) * PW;
+    prel[k] = ((py * p.cw + px) * 64 + lch * 8) * 2;
+    pyx[k] = pp < PHW ? (py | (px << 16)) : 0xffff;
+  }
+  uintptr_t zline = reinterpret_cast<uintptr_t>(g_zero_conv);
+  asm volatile("" : "+v"(zline));  // kept in registers: not re-read from the GOT at every issue
+  auto load_patch = [&](int tt, int buf, auto asm_tag) __attribute__((always_inline)) {
     const int tx = tt % tiles_x, r = tt / tiles_x;
     const int ty = r % tiles_y, b = r / tiles_y;
     const int iy0 = ty * TYP - 1, ix0 = tx * TW - 1;
-    const f16* img = reinterpret_cast<const f16*>(p.A) + (size_t)b * imgsz;
+    // address of the patch's first pixel (outside the map for border tiles: used under `ok` only)
+    const uintptr_t org = reinterpret_cast<uintptr_t>(p.A) +
+                          (uintptr_t)(((long long)b * (long long)imgsz + ((long long)iy0 * p.cw + ix0) * 64) * 2);
     char* dst = smem + buf * PATCH;
-    for (int q = wave; q < PINS; q += NW) {
-      const int pp = q * RWP + lrow;
-      const int py = pp / PW, px = pp - (pp / PW) * PW;
-      const int iy = iy0 + py, ix = ix0 + px;
-      const bool ok = pp < PHW && iy >= 0 && iy < p.ch && ix >= 0 && ix < p.cw;
-      const f16* src = ok ? img + ((size_t)iy * p.cw + ix) * 64 + lch * 8 : g_zero_conv;
-      if constexpr (decltype(asm_tag)::value)
-        glds16_asm(src, __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dst + q * RWP * ROWB)));
-      else
-        glds16(src, dst + q * RWP * ROWB);
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+      const int q = wave + k * NW;
+      if (k < PINS / NW || q < PINS) {  // (the last group: the first PINS % NW waves)
+        const int iy = iy0 + (pyx[k] & 0xffff), ix = ix0 + (pyx[k] >> 16);
+        const bool ok = (unsigned)iy < (unsigned)p.ch && (unsigned)ix < (unsigned)p.cw;
+        const void* src = reinterpret_cast<const void*>(ok ? org + (uintptr_t)(long long)prel[k] : zline);
+        if constexpr (decltype(asm_tag)::value)
+          glds16_asm(src, __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dst + q * RWP * ROWB)));
+        else
+          glds16(src, dst + q * RWP * ROWB);
+      }
     }
   };
   // MODE 0: ReLU of a landed patch, in place (callers barrier before and after)
@@ -502,6 +538,20 @@ conv64p_kernel(const GemmParams p) {
 #pragma unroll
   for (int j = 0; j < TN; ++j)
     bias[j] = p.bias ? *reinterpret_cast<const float4*>(p.bias + j * 16 + (lane >> 4) * 4) : float4{0.f, 0.f, 0.f, 0.f};
+  // FOLD: the 1x1's weights as A fragments -- row j 16 + (lane & 15), logical
+  // chunk 4 s + (lane >> 4) -- and its bias in the accumulator layout
+  f16x8 pww[FOLD ? TN : 1][2];
+  float4 pwb[FOLD ? TN : 1];
+  if constexpr (FOLD) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2)
+        pww[j][s2] = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.pw_w) +
+                                                     (size_t)(j * 16 + (lane & 15)) * p.pw_ldw + (4 * s2 + (lane >> 4)) * 8);
+      pwb[j] = p.pw_bias ? *reinterpret_cast<const float4*>(p.pw_bias + j * 16 + (lane >> 4) * 4) : float4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
 
   load_patch(t, 0, std::false_type{});
   wait_vm_n<0>();
@@ -511,144 +561,244 @@ conv64p_kernel(const GemmParams p) {
     lds_barrier();
   }
 
-  // one tile: MFMAs on patch buffer BUF while the next tile's patch lands in
-  // the other; returns true when the workgroup's run is done
-  auto step = [&](auto buf_tag) -> bool {
-    constexpr int BUF = decltype(buf_tag)::value;
-    const int tn = t + g8;
-    // (every wave's epilogue staging in BUF ^ 1 was read before the barrier
-    // that ended the previous tile)
-    if (tn < tend) load_patch(tn, BUF ^ 1, std::true_type{});
-
-    const int tx = t % tiles_x, r = t / tiles_x;
-    const int ty = r % tiles_y, b = r / tiles_y;
-    // output row (pixel) of read-back row it * 8 + rr of this wave, or -1
-    int mo[4];
+  // MODE 0: ReLU of the rows this wave's own DMAs brought in (load_patch's
+  // row groups q = wave, wave + NW, ...: one wave-instruction = 64 lanes x 16 B)
+  // -- every wave has NFULL groups, the first PINS - NFULL NW waves one more;
+  // the reads of the full groups go out together
+  auto relu_own = [&](int buf) __attribute__((always_inline)) {
+    constexpr int NFULL = PINS / NW;
+    char* const base = smem + buf * PATCH + wave * RWP * ROWB + lane * 16;
+    f16x8 v[NFULL];
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int row = it * 8 + rr;
-      const int oy = ty * TYP + wave * TM + (row >> 4), ox = tx * TW + (row & 15);
-      mo[it] = (oy < Ho && ox < Wo) ? ((b * Ho + oy) * Wo + ox) : -1;
-    }
-    // residual rows, loaded now and consumed after the MFMAs on every path
-    f16x8 res[NRES > 0 ? NRES : 1][4];
-    if constexpr (NRES > 0) {
+    for (int k = 0; k < NFULL; ++k) v[k] = *reinterpret_cast<const f16x8*>(base + k * NW * RWP * ROWB);
 #pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const size_t o = (size_t)(mo[it] < 0 ? 0 : mo[it]) * p.ldo + c8 * 8;
-        res[0][it] = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.res0) + o);
-        if constexpr (NRES > 1) res[1][it] = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.res1) + o);
-      }
+    for (int k = 0; k < NFULL; ++k) *reinterpret_cast<f16x8*>(base + k * NW * RWP * ROWB) = relu8(v[k]);
+    if (wave + NFULL * NW < PINS) {
+      f16x8* const w = reinterpret_cast<f16x8*>(base + NFULL * NW * RWP * ROWB);
+      *w = relu8(*w);
     }
-    __builtin_amdgcn_sched_barrier(0);  // issue the loads here, not sunk next to their use behind the MFMAs
+  };
 
-    f32x4 acc[TM][TN];
+  // the wave's tile a (bias bs added, ReLU'd under relu_tag) rounded to f16,
+  // parked in its staging slice and stored as whole rows: row r at r * 128,
+  // 16-B chunk c swizzled by (r & 7).  sink_tag: rows outside the map are
+  // stored to the sink line (a fixed number of stores: the counted wait)
+  auto store_rows16 = [&](const f32x4(&a)[TM][TN], const float4(&bs)[TN], f16* o, char* stage, const int(&mo)[4],
+                          auto relu_tag, auto sink_tag) __attribute__((always_inline)) {
+    constexpr bool RELU = decltype(relu_tag)::value, SINK = decltype(sink_tag)::value;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < TN; ++j) {
+        const float4 bn = bs[j];
+        const float v0 = a[i][j][0] + bn.x, v1 = a[i][j][1] + bn.y;
+        const float v2 = a[i][j][2] + bn.z, v3 = a[i][j][3] + bn.w;
+        const f16x4 h = RELU ? f16x4{(f16)(v0 > 0.f ? v0 : 0.f), (f16)(v1 > 0.f ? v1 : 0.f),
+                                     (f16)(v2 > 0.f ? v2 : 0.f), (f16)(v3 > 0.f ? v3 : 0.f)}
+                             : f16x4{(f16)v0, (f16)v1, (f16)v2, (f16)v3};
+        const int row = i * 16 + (lane & 15), q = j * 4 + (lane >> 4);  // 8-B column quad
+        *reinterpret_cast<f16x4*>(stage + row * 128 + ((((q >> 1) ^ (row & 7)) << 4) | ((q & 1) << 3))) = h;
+      }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int ky = tap / 3, kx = tap - (tap / 3) * 3;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        f16x8 fa[TM], fb[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const int e = 2 * (i + ky) + kx;
-          fa[i] = *reinterpret_cast<const f16x8*>(smem + pa[e & 7][s2] + (BUF * PATCH + ((i + ky) * PW + kx) * ROWB));
-          if constexpr (MODE == 0 && !MDE_CONVP_RELU_PASS) fa[i] = relu8(fa[i]);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          fb[j] = *reinterpret_cast<const f16x8*>(smem + (tap < 8 ? wa[s2] + tap * 64 * ROWB : wa8[s2]) + j * 16 * ROWB);
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma16x16x32(fb[j], fa[i], acc[i][j]);  // (tap MFMAs)
+    for (int it = 0; it < 4; ++it) {
+      const int row = it * 8 + rr;
+      const f16x8 h = *reinterpret_cast<const f16x8*>(stage + row * 128 + ((c8 ^ (row & 7)) << 4));
+      if constexpr (SINK) {
+        *(mo[it] >= 0 ? reinterpret_cast<f16x8*>(o + (size_t)mo[it] * p.ldo + c8 * 8) : g_sink_conv + lane) = h;
+      } else {
+        if (mo[it] >= 0) *reinterpret_cast<f16x8*>(o + (size_t)mo[it] * p.ldo + c8 * 8) = h;
       }
     }
-    // (the epilogue's residual conversions stay below: hoisted among the
-    // MFMAs they would wait for the loads -- and, in order, the prefetch)
-    __builtin_amdgcn_sched_barrier(0);
-    // the next patch landed (own DMAs; the previous tile's stores and this
-    // tile's residual loads, all issued before the MFMAs, too) -- after the
-    // barrier every wave's DMAs and patch reads are done: the epilogue may
-    // stage in this buffer and the next tile read the other
-    wait_vm_n<0>();
-    lds_barrier();
-    if constexpr (MODE == 0) {
-      if (MDE_CONVP_RELU_PASS && tn < tend) relu_patch(BUF ^ 1);
-    }
+  };
 
-    char* stage = smem + BUF * PATCH + wave * EPIW;
-    f16* const out = reinterpret_cast<f16*>(p.out16);
-    if constexpr (F16STAGE) {
-      // f16 rows: row r at r * 128, 16-B chunk c swizzled by (r & 7)
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const float4 bn = bias[j];
-          const float v0 = acc[i][j][0] + bn.x, v1 = acc[i][j][1] + bn.y;
-          const float v2 = acc[i][j][2] + bn.z, v3 = acc[i][j][3] + bn.w;
-          const f16x4 h = MODE == 0 ? f16x4{(f16)(v0 > 0.f ? v0 : 0.f), (f16)(v1 > 0.f ? v1 : 0.f),
-                                            (f16)(v2 > 0.f ? v2 : 0.f), (f16)(v3 > 0.f ? v3 : 0.f)}
-                                    : f16x4{(f16)v0, (f16)v1, (f16)v2, (f16)v3};
-          const int row = i * 16 + (lane & 15), q = j * 4 + (lane >> 4);  // 8-B column quad
-          *reinterpret_cast<f16x4*>(stage + row * 128 + ((((q >> 1) ^ (row & 7)) << 4) | ((q & 1) << 3))) = h;
-        }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
+  // one tile: MFMAs on patch buffer BUF while the next tile's patch lands in
+  // the other; returns true when the workgroup's run is done.
+  // PIPE (MODE 0 and 3, no register loads in the loop): the prefetch stays in
+  // flight under the epilogue --
+  //   issue the prefetch | tap MFMAs | barrier: every wave has read BUF |
+  //   epilogue staged in BUF, 4 row stores per wave | counted wait: all but
+  //   those 4 stores, i.e. this wave's own patch DMAs | MODE 0: ReLU of the
+  //   rows they brought | end-of-tile barrier: the landed, ReLU'd patch is
+  //   published and the staging reads are retired.
+  // The count needs a fixed number of stores behind the DMAs: rows outside the
+  // map are stored to a sink line, not skipped.
+  // MODE 1 and 2 keep the wait in front of the epilogue: their residual loads
+  // sit behind the DMAs in the (in-order) vmcnt queue, so the first use drains
+  // the prefetch wherever the wait is; issued ahead of the DMAs, hipcc, which
+  // does not see the asm DMAs, waits for them with counts of 3 and less.
+  // A wave whose two tile rows lie below the map (the bottom tile row: 148 =
+  // 9 x 16 + 4 leaves six of eight waves without a row) runs neither the tap
+  // loop nor the epilogue; it issues its share of the prefetch, waits for it
+  // and reaches both barriers.
+  auto step = [&](auto buf_tag) -> bool {
+    constexpr int BUF = decltype(buf_tag)::value;
+    constexpr bool PIPE = NRES == 0;
+    const int tn = t + g8;
+    const bool more = tn < tend;
+    // (every wave's epilogue staging in BUF ^ 1 was read before the barrier
+    // that ended the previous tile)
+    if (more) load_patch(tn, BUF ^ 1, std::true_type{});
+
+    const int tx = t % tiles_x, r = t / tiles_x;
+    const int ty = r % tiles_y, b = r / tiles_y;
+    if (ty * TYP + wave * TM < Ho) {  // wave-uniform
+      // output row (pixel) of read-back row it * 8 + rr of this wave, or -1
+      int mo[4];
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int row = it * 8 + rr;
-        const f16x8 h = *reinterpret_cast<const f16x8*>(stage + row * 128 + ((c8 ^ (row & 7)) << 4));
-        if (mo[it] >= 0) *reinterpret_cast<f16x8*>(out + (size_t)mo[it] * p.ldo + c8 * 8) = h;
+        const int oy = ty * TYP + wave * TM + (row >> 4), ox = tx * TW + (row & 15);
+        mo[it] = (oy < Ho && ox < Wo) ? ((b * Ho + oy) * Wo + ox) : -1;
+      }
+      // residual rows, loaded now and consumed after the MFMAs on every path
+      f16x8 res[NRES > 0 ? NRES : 1][4];
+      if constexpr (NRES > 0) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          const size_t o = (size_t)(mo[it] < 0 ? 0 : mo[it]) * p.ldo + c8 * 8;
+          res[0][it] = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.res0) + o);
+          if constexpr (NRES > 1) res[1][it] = *reinterpret_cast<const f16x8*>(reinterpret_cast<const f16*>(p.res1) + o);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);  // issue the loads here, not sunk next to their use behind the MFMAs
+
+      f32x4 acc[TM][TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int ky = tap / 3, kx = tap - (tap / 3) * 3;
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          f16x8 fa[TM], fb[TN];
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            const int e = 2 * (i + ky) + kx;
+            fa[i] = *reinterpret_cast<const f16x8*>(smem + pa[e & 7][s2] + (BUF * PATCH + ((i + ky) * PW + kx) * ROWB));
+            if constexpr (MODE == 0 && !MDE_CONVP_RELU_PASS) fa[i] = relu8(fa[i]);
+          }
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            fb[j] = *reinterpret_cast<const f16x8*>(smem + (tap < 8 ? wa[s2] + tap * 64 * ROWB : wa8[s2]) + j * 16 * ROWB);
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] = mfma16x16x32(fb[j], fa[i], acc[i][j]);  // (tap MFMAs)
+        }
+      }
+      // (the epilogue's residual conversions stay below: hoisted among the
+      // MFMAs they would wait for the loads -- and, in order, the prefetch)
+      __builtin_amdgcn_sched_barrier(0);
+      // MODE 1, 2: the next patch landed (own DMAs; the previous tile's stores
+      // and this tile's residual loads, all issued before the MFMAs, too).
+      // After the barrier every wave's patch reads are done: the epilogue may
+      // stage in this buffer
+      if constexpr (!PIPE) wait_vm_n<0>();
+      lds_barrier();
+
+      char* stage = smem + BUF * PATCH + wave * EPIW;
+      f16* const out = reinterpret_cast<f16*>(p.out16);
+      if constexpr (F16STAGE) {
+        store_rows16(acc, bias, out, stage, mo, std::integral_constant<bool, MODE == 0>{}, std::true_type{});
+      } else {
+        // fp32 rows of 256 B, 16-B chunk c swizzled by (r & 7); two passes of
+        // 16 rows (accumulator row block i)
+        f16x8 hh[FOLD ? 4 : 1];  // FOLD: the finished rows it * 8 + rr, kept until both passes have read the slice
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          if (i > 0) __builtin_amdgcn_wave_barrier();  // pass 0's reads before pass 1 overwrites the slice
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            const float4 bn = bias[j];
+            const f32x4 v = {acc[i][j][0] + bn.x, acc[i][j][1] + bn.y, acc[i][j][2] + bn.z, acc[i][j][3] + bn.w};
+            const int row = lane & 15, q = j * 4 + (lane >> 4);  // 16-B chunk
+            *reinterpret_cast<f32x4*>(stage + row * 256 + ((q ^ (row & 7)) << 4)) = v;
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int h2 = 0; h2 < 2; ++h2) {
+            const int it = i * 2 + h2, row = h2 * 8 + rr;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(stage + row * 256 + (((2 * c8) ^ (row & 7)) << 4));
+            const f32x4 bb = *reinterpret_cast<const f32x4*>(stage + row * 256 + (((2 * c8 + 1) ^ (row & 7)) << 4));
+            float v[8] = {a[0], a[1], a[2], a[3], bb[0], bb[1], bb[2], bb[3]};
+            const f16x8 r0 = res[0][it];
+            if (p.res0_relu) {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] += fmaxf((float)r0[e], 0.f);
+            } else {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] += (float)r0[e];
+            }
+            if constexpr (NRES > 1) {
+              const f16x8 r1 = res[NRES - 1][it];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] += (float)r1[e];
+            }
+            f16x8 h;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = (f16)v[e];
+            if constexpr (FOLD) hh[it] = h;
+            else if (mo[it] >= 0) *reinterpret_cast<f16x8*>(out + (size_t)mo[it] * p.ldo + c8 * 8) = h;
+          }
+        }
+        if constexpr (FOLD) {
+          __builtin_amdgcn_wave_barrier();  // pass 1's reads before the f16 rows overwrite the slice
+#pragma unroll
+          for (int it = 0; it < 4; ++it) {
+            const int row = it * 8 + rr;
+            *reinterpret_cast<f16x8*>(stage + row * 128 + ((c8 ^ (row & 7)) << 4)) = hh[it];
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+          f16x8 fp[TM][2];
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+              const int row = i * 16 + (lane & 15);
+              fp[i][s2] = *reinterpret_cast<const f16x8*>(stage + row * 128 + (((4 * s2 + (lane >> 4)) ^ (row & 7)) << 4));
+            }
+          f32x4 a2[TM][TN];
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) a2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+              for (int j = 0; j < TN; ++j) a2[i][j] = mfma16x16x32(pww[j][s2], fp[i][s2], a2[i][j]);
+          __builtin_amdgcn_wave_barrier();  // the fragment reads before the 1x1's rows are parked
+          store_rows16(a2, pwb, reinterpret_cast<f16*>(p.pw_out), stage, mo, std::false_type{}, std::false_type{});
+        }
+      }
+      // PIPE: own patch DMAs landed -- they are older than the 4 row stores,
+      // which stay in flight
+      if constexpr (PIPE) {
+        if (more) wait_vm_n<4>();
       }
     } else {
-      // fp32 rows of 256 B, 16-B chunk c swizzled by (r & 7); two passes of
-      // 16 rows (accumulator row block i)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        if (i > 0) __builtin_amdgcn_wave_barrier();  // pass 0's reads before pass 1 overwrites the slice
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const float4 bn = bias[j];
-          const f32x4 v = {acc[i][j][0] + bn.x, acc[i][j][1] + bn.y, acc[i][j][2] + bn.z, acc[i][j][3] + bn.w};
-          const int row = lane & 15, q = j * 4 + (lane >> 4);  // 16-B chunk
-          *reinterpret_cast<f32x4*>(stage + row * 256 + ((q ^ (row & 7)) << 4)) = v;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          const int it = i * 2 + h2, row = h2 * 8 + rr;
-          const f32x4 a = *reinterpret_cast<const f32x4*>(stage + row * 256 + (((2 * c8) ^ (row & 7)) << 4));
-          const f32x4 bb = *reinterpret_cast<const f32x4*>(stage + row * 256 + (((2 * c8 + 1) ^ (row & 7)) << 4));
-          float v[8] = {a[0], a[1], a[2], a[3], bb[0], bb[1], bb[2], bb[3]};
-          const f16x8 r0 = res[0][it];
-          if (p.res0_relu) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += fmaxf((float)r0[e], 0.f);
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += (float)r0[e];
-          }
-          if constexpr (NRES > 1) {
-            const f16x8 r1 = res[NRES - 1][it];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] += (float)r1[e];
-          }
-          f16x8 h;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) h[e] = (f16)v[e];
-          if (mo[it] >= 0) *reinterpret_cast<f16x8*>(out + (size_t)mo[it] * p.ldo + c8 * 8) = h;
-        }
+      // no output row: the same barrier and wait in the same order (PIPE: no
+      // stores behind the DMAs, and the others' epilogues do not wait for them)
+      if constexpr (PIPE) {
+        lds_barrier();
+        if (more) wait_vm_n<0>();
+      } else {
+        wait_vm_n<0>();
+        lds_barrier();
       }
     }
-    if (tn >= tend) return true;
-    lds_barrier();  // staging reads retired before the next prefetch overwrites them; the next patch is ReLU'd (stores stay in flight)
+    if (!more) return true;
+    if constexpr (MODE == 0) {
+      if (MDE_CONVP_RELU_PASS) relu_own(BUF ^ 1);
+    }
+    lds_barrier();  // staging reads retired before the next prefetch overwrites them; the next patch landed and ReLU'd (stores stay in flight)
     t = tn;
     return false;
   };
@@ -666,7 +816,7 @@ conv64p_kernel(const GemmParams p) {
 int conv64p_mode(const GemmParams& p) {
   const int mode = knob(KNOB_CONV_PERSIST);
   if (!mode || p.amode != A_CONV3 || p.emode != E_STORE || p.stride != 1 || p.N != 64 || p.cc != 64 ||
-      p.ch != p.oh || p.cw != p.ow || p.ldo < 64 || (p.ldo & 7) || p.res0_rows > 0)
+      p.ch != p.oh || p.cw != p.ow || p.ch >= 32768 || p.cw >= 32768 || p.ldo < 64 || (p.ldo & 7) || p.res0_rows > 0)
     return -1;
   const bool r1 = p.res1 || p.res1_up;
   int m;
@@ -680,11 +830,30 @@ int conv64p_mode(const GemmParams& p) {
   return m;
 }
 
+// the persistent conv runs a following 64 -> 64 1x1 conv (GemmParams::pw_*) on
+// its tiles: bias + res0 problems on 16 x 16 tiles (switch "outconv_fold")
+bool folds_pointwise(const GemmParams& p) {
+  return knob(KNOB_OUTCONV_FOLD) && knob(KNOB_CONV_PERSIST) == 1 && conv64p_mode(p) == 1;
+}
+
 bool conv64p_launch(const GemmParams& p, hipStream_t st, hipError_t& err) {
+  const dim3 grid(256);
+  if (p.pw_w) {
+    const dim3 block(512);
+    // a folded 1x1 the kernel cannot take is an error, never dropped
+    if (!folds_pointwise(p) || !p.pw_out || p.pw_ldw < 64 || (p.pw_ldw & 7) || ((uintptr_t)p.pw_w & 15) ||
+        ((uintptr_t)p.pw_out & 15)) {
+      err = hipErrorInvalidValue;
+      return true;
+    }
+    hipLaunchKernelGGL((conv64p_kernel<16, 1, true>), grid, block, 0, st, p);
+    err = hipGetLastError();
+    return true;
+  }
   const int m = conv64p_mode(p);
   if (m < 0) return false;
   const int typ = knob(KNOB_CONV_PERSIST) == 2 ? 8 : 16;
-  const dim3 grid(256), block(typ * 32);
+  const dim3 block(typ * 32);
   if (typ == 16) {
     if (m == 0) hipLaunchKernelGGL((conv64p_kernel<16, 0>), grid, block, 0, st, p);
     else if (m == 1) hipLaunchKernelGGL((conv64p_kernel<16, 1>), grid, block, 0, st, p);
@@ -1120,6 +1289,8 @@ bool conv_direct_supported(const GemmParams& p) {
 // 256-channel 148^2 conv paid more for the 32 gathers per pixel than the
 // launch costs (3.187 -> 3.197 ms), so wider maps keep the launch
 // (profiles/r06_resize_fold.txt).
+bool conv64p_folds_pointwise(const GemmParams& p) { return folds_pointwise(p); }
+
 bool conv3_takes_res1_up(const GemmParams& p) {
   return knob(KNOB_RESIZE_FOLD) && p.amode == A_CONV3 && p.emode == E_STORE && p.stride == 1 && p.N <= 64 &&
          conv_direct_supported(p) && conv64p_mode(p) < 0 && p.ldo == p.N && (p.N & 7) == 0 && p.res1_uh > 0 &&

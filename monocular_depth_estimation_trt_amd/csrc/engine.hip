@@ -324,13 +324,18 @@ bool Runner::dpt_fusion(DptMaps& m, int n, int r, bool relu_res, bool fold_resiz
     rcu(p + ".rcu1", x1, x0, m.sb, m.tb, n, h, w, F, relu_res, x0_up, uh, uw);
     s = m.sb;
   }
-  rcu(p + ".rcu2", s, nullptr, m.ub, m.tb, n, h, w, F, relu_res);
-  GemmParams g = dense(m.ub, F, p + ".out.w", n * h * w, F, F);
-  g.emode = E_STORE;
-  g.bias = w32(p + ".out.b");
-  g.out16 = m.vb;
-  g.ldo = F;
-  gemm((p + ".out").c_str(), g);
+  // out_conv: run by rcu2's second conv on its tiles where that is the
+  // persistent 64-channel conv (switch "outconv_fold": no ".out" step, ub not
+  // written), else a GEMM over ub
+  const std::string ow = p + ".out.w";
+  if (!rcu(p + ".rcu2", s, nullptr, m.ub, m.tb, n, h, w, F, relu_res, nullptr, 0, 0, &ow, m.vb)) {
+    GemmParams g = dense(m.ub, F, ow, n * h * w, F, F);
+    g.emode = E_STORE;
+    g.bias = w32(p + ".out.b");
+    g.out16 = m.vb;
+    g.ldo = F;
+    gemm((p + ".out").c_str(), g);
+  }
   if (!dst) return false;
   if (fold_resize) return true;  // vb stays intact until the next block's rcu1 has read it
   step((p + ".resize").c_str(), [&] { return launch_resize(m.vb, dst, n, h, w, F, dpt_h(r - 2), dpt_w(r - 2), st); });

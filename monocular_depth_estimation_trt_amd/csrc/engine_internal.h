@@ -343,7 +343,8 @@ struct Runner {
   }
   void dav2_head32(int B, float* out);
 
-  void gemm(const char* name, const GemmParams& g) {
+  // g as gemm() launches it: E_STORE problems get the split-K workspace
+  GemmParams with_split_ws(const GemmParams& g) const {
     GemmParams q = g;
     if (split_ws && g.emode == E_STORE && !g.partial) {
       q.partial = split_ws;
@@ -352,6 +353,10 @@ struct Runner {
       q.tile_cnt = split_counters(split_ws);
       q.tile_cnt_cap = kTileCnt;
     }
+    return q;
+  }
+  void gemm(const char* name, const GemmParams& g) {
+    const GemmParams q = with_split_ws(g);
     step(name, [&] { return launch_gemm(q, st); });
   }
 
@@ -362,8 +367,13 @@ struct Runner {
   // extra_up (GemmParams::res1_up): extra is the bilinear upsample of extra_up
   // [B][uh][uw][F], read on the fly where the conv route allows (else written
   // into extra first)
-  void rcu(const std::string& pfx, const h16* x, const h16* extra, h16* out, h16* tmp, int B, int h, int w, int F,
-           bool relu_res = false, const h16* extra_up = nullptr, int uh = 0, int uw = 0) {
+  // pw (name of dense 64 x 64 weights "X.w", bias "X.b") / pw_out: a 1x1 conv
+  // that follows the unit.  Returns true when the second conv ran it on its
+  // tiles (GemmParams::pw_*): pw_out holds the 1x1's result and `out` is not
+  // written; false: `out` holds the unit's result and the caller runs the 1x1
+  bool rcu(const std::string& pfx, const h16* x, const h16* extra, h16* out, h16* tmp, int B, int h, int w, int F,
+           bool relu_res = false, const h16* extra_up = nullptr, int uh = 0, int uw = 0,
+           const std::string* pw = nullptr, h16* pw_out = nullptr) {
     GemmParams g1 = conv(x, B, h, w, F, pfx + ".c1.w", F, 1);
     g1.relu_in = 1;
     g1.bias = w32_opt(pfx + ".c1.b");
@@ -379,7 +389,15 @@ struct Runner {
     g2.res1_uh = uh;
     g2.res1_uw = uw;
     g2.out16 = out;
+    const bool fold = pw && F == 64 && conv_folds_pointwise(with_split_ws(g2));
+    if (fold) {
+      g2.pw_w = w16(*pw);
+      g2.pw_ldw = ldw(*pw);
+      g2.pw_bias = w32(pw->substr(0, pw->size() - 1) + "b");
+      g2.pw_out = pw_out;
+    }
     gemm((pfx + ".c2").c_str(), g2);
+    return fold;
   }
 
   // the f16 transformer block of every family (engine.hip)

@@ -790,6 +790,8 @@ thread_local GemmRoute t_last_route;
 hipError_t gemm_route(const GemmParams& p, GemmRoute& r) {
   const auto take = [&r](const GemmRoute& x) { r = x; return hipSuccess; };
   if (p.M <= 0 || p.N <= 0) return take({ROUTE_NONE});
+  // a folded 1x1 (pw_*) exists in the persistent conv only
+  if (p.pw_w && !conv_folds_pointwise(p)) return hipErrorInvalidValue;
   if (p.res1_up) {
     // res1 = upsample(res1_up): read through it by the direct conv's
     // epilogue, or written into res1 first for every other route
@@ -835,6 +837,11 @@ hipError_t gemm_route(const GemmParams& p, GemmRoute& r) {
   const Tile t = pick_tile(p);  // (E_PARTIAL is the split routes' own: not a caller's mode)
   if (p.emode == E_PARTIAL || !tile_has(t, p.amode, p.emode, false)) return hipErrorInvalidValue;
   return take(tile_route(ROUTE_TILE, t, 1, false));
+}
+
+bool conv_folds_pointwise(const GemmParams& p) {
+  return p.amode == A_CONV3 && p.emode == E_STORE && !p.res1_up && conv64p_folds_pointwise(p) &&
+         store_split_slices(p) <= 1 && conv_direct_supported(p) && !prefer_im2col(p);
 }
 
 const GemmRoute& gemm_last_route() { return t_last_route; }

@@ -53,6 +53,13 @@ struct GemmParams {
   // upsample in its epilogue; every other path first writes the upsample into
   // res1 (launch_gemm), so res1 must be a buffer of the output's shape either way
   const h16* res1_up = nullptr; int res1_uh = 0, res1_uw = 0;
+  // a 64 -> 64 1x1 conv folded behind a 3x3 conv (switch "outconv_fold": the
+  // DPT fusion blocks' out_conv behind rcu2's second conv): pw_out [M][ldo] =
+  // f16(pw_w . f16(conv epilogue) + pw_bias), pw_w = [64][pw_ldw] dense-GEMM
+  // weights; out16 is then not written.  Only the persistent conv runs it --
+  // set the fields when conv_folds_pointwise(p) says so, any other route
+  // rejects them
+  const h16* pw_w = nullptr; int pw_ldw = 0; const float* pw_bias = nullptr; h16* pw_out = nullptr;
   float* x32 = nullptr; const float* ls = nullptr;
   // f16 residual stream: when set, E_RESID / E_PATCH update / write xh
   // [m][ldo] f16 instead of x32 (DA-V2 engines with an f16 residual)
@@ -165,6 +172,12 @@ bool conv_direct_supported(const GemmParams& p);
 // the direct conv takes p's res1 through GemmParams::res1_up (conv.hip)
 bool conv3_takes_res1_up(const GemmParams& p);
 hipError_t launch_conv3(const GemmParams& p, hipStream_t st);
+// the persistent 64-channel conv (conv.hip) takes p and would run a following
+// 1x1 (GemmParams::pw_*) on its tiles
+bool conv64p_folds_pointwise(const GemmParams& p);
+// launch_gemm routes p to that kernel with the fold available (gemm.hip): the
+// caller may then attach the 1x1 (pw_*) instead of launching it
+bool conv_folds_pointwise(const GemmParams& p);
 
 // A-stationary panel GEMM (gemm_panel.hip) for K = 384 token-major E_STORE /
 // E_QKV problems at large batch (the ViT-S fc1 and qkv); launch_gemm routes there when

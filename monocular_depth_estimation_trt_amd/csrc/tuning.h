@@ -74,6 +74,11 @@ enum Knob : int {
   // four taps) instead of a resize launch (1: on).  Same bits.
   // test_resize_fold_bit_exact, test_conv_res1_up (op level, against torch)
   KNOB_RESIZE_FOLD,
+  // the DPT fusion blocks' 1x1 out_conv run by rcu2's second conv on its
+  // tiles where that conv is the persistent 64-channel kernel
+  // (GemmParams::pw_*) instead of a GEMM launch over the map it has just
+  // written (1: on).  Same bits.  test_outconv_fold_bit_exact
+  KNOB_OUTCONV_FOLD,
   KNOB_COUNT
 };
 

@@ -35,6 +35,7 @@ constexpr KnobDef kKnobs[KNOB_COUNT] = {
     {"splitk_fused", "MDE_SPLITK_FUSED", 0, 0, 1},
     {"attn_tail", "MDE_ATTN_TAIL", 2, 0, 2},
     {"resize_fold", "MDE_RESIZE_FOLD", 1, 0, 1},
+    {"outconv_fold", "MDE_OUTCONV_FOLD", 1, 0, 1},
 };
 
 std::atomic<int> g_val[KNOB_COUNT];

@@ -7,6 +7,14 @@ engine runs it before the resize (4x fewer MACs, exact by linearity).  These
 are the numbers roofline fractions are quoted against (ViT-S
 115.27 GFLOP/img, ViT-L 1304.22 GFLOP/img at 518^2).
 
+Omission: where the engine runs a fusion block's out_conv inside rcu2's second
+conv (switch "outconv_fold" on a persistent-conv grid: no rfN.out step), the
+1x1's work is still listed under rfN.out, not under rfN.rcu2.c2 -- whether
+the fold is active depends on the library's dispatch switches as well as on
+the grid, and layer_flops() takes neither.  The totals are unaffected; a
+per-layer table of such a run shows rfN.rcu2.c2 without the 1x1's FLOPs and
+no rfN.out row.
+
 Layer names match the engine's profiler names (csrc/engine.hip: Runner::forward_dav2 and the
 shared vit_block / dpt_* steps; pinned by tests/golden/layer_schedule.json).
 """

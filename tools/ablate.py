@@ -24,7 +24,7 @@ sys.path.insert(0, ROOT)
 # name -> (file, [(old, new, count)])
 VARIANTS = {
     # persistent RCU conv: no next-patch prefetch (MFMAs re-read the last patch)
-    "cp_nopf": ("conv.hip", [("    if (tn < tend) load_patch(tn, BUF ^ 1, std::true_type{});\n", "", 1)]),
+    "cp_nopf": ("conv.hip", [("    if (more) load_patch(tn, BUF ^ 1, std::true_type{});\n", "", 1)]),
     # persistent RCU conv: no tap MFMAs (fragments kept live)
     "cp_nomfma": ("conv.hip", [
         ("acc[i][j] = mfma16x16x32(fb[j], fa[i], acc[i][j]);  // (tap MFMAs)",
@@ -36,7 +36,17 @@ VARIANTS = {
     # persistent RCU conv: no output stores (values kept live)
     "cp_nostore": ("conv.hip", [
         ("if (mo[it] >= 0) *reinterpret_cast<f16x8*>(out + (size_t)mo[it] * p.ldo + c8 * 8) = h;",
-         'asm volatile("" :: "v"(h));', 2)]),
+         'asm volatile("" :: "v"(h));', 1),
+        ("*(mo[it] >= 0 ? reinterpret_cast<f16x8*>(o + (size_t)mo[it] * p.ldo + c8 * 8) : g_sink_conv + lane) = h;",
+         'asm volatile("" :: "v"(h));', 1),
+        ("if (mo[it] >= 0) *reinterpret_cast<f16x8*>(o + (size_t)mo[it] * p.ldo + c8 * 8) = h;",
+         'asm volatile("" :: "v"(h));', 1)]),
+    # persistent RCU conv: no epilogue at all (a never-true uniform condition
+    # keeps its code and the accumulators live; without its stores the counted
+    # wait no longer covers the patch DMAs)
+    "cp_noepi": ("conv.hip", [
+        ("      if constexpr (F16STAGE) {\n        store_rows16(",
+         "      if (p.cb < 0)\n      if constexpr (F16STAGE) {\n        store_rows16(", 1)]),
     # attention: the softmax exponentials replaced by their argument
     "attn_noexp": ("attention.hip", [
         ("const float p0 = __builtin_amdgcn_exp2f(sc[r]), p1 = __builtin_amdgcn_exp2f(sc[r + 1]);",
