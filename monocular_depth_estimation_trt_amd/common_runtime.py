@@ -8,6 +8,7 @@ Same names, same argument meaning, same error behaviour:
   free_buffers(inputs, outputs, stream)               (:179-182)
   memcpy_host_to_device / memcpy_device_to_host       (:186-193)
   StageTimer                                          (:196-238)
+  EventPair(stream)           one timed region between two hipEvents
   _do_inference_base / do_inference                   (:241-275)
 A failing runtime call raises RuntimeError with the HIP error text
 (`cuda_call`/`check_cuda_err`, :41-56); size mismatches raise ValueError.
@@ -26,7 +27,7 @@ from . import _lib
 from .engine import DataType, Engine, TensorIOMode, nptype, volume
 
 __all__ = ["HostDeviceMem", "allocate_buffers", "free_buffers", "memcpy_host_to_device",
-           "memcpy_device_to_host", "StageTimer", "do_inference", "_do_inference_base", "hip_call",
+           "memcpy_device_to_host", "StageTimer", "EventPair", "do_inference", "_do_inference_base", "hip_call",
            "stream_create", "stream_destroy", "stream_synchronize", "volume", "nptype", "DataType",
            "TensorIOMode"]
 
@@ -195,6 +196,49 @@ class StageTimer:
         for e in self._events:
             hip_call("mde_rt_event_destroy", e)
         self._events = []
+
+
+class EventPair:
+    """A hipEvent pair around one region of work on `stream`:
+
+        with EventPair(stream) as ev:   # marks the start
+            ...enqueue...
+            ev.stop()                   # marks the end
+            stream_synchronize(stream)
+            ms = ev.ms()
+
+    ms() is only valid after the stream has synchronized past stop(); the
+    events are destroyed when the block ends, however it ends."""
+
+    def __init__(self, stream: int):
+        self._stream = C.c_void_p(int(stream or 0))
+        self._events = []
+
+    def __enter__(self):
+        try:
+            for _ in range(2):
+                e = C.c_void_p()
+                hip_call("mde_rt_event_create", C.byref(e))
+                self._events.append(e)
+            hip_call("mde_rt_event_record", self._events[0], self._stream)
+        except Exception:
+            self.__exit__()
+            raise
+        return self
+
+    def stop(self) -> None:
+        hip_call("mde_rt_event_record", self._events[1], self._stream)
+
+    def ms(self) -> float:
+        ms = C.c_float()
+        hip_call("mde_rt_event_elapsed_ms", C.byref(ms), self._events[0], self._events[1])
+        return float(ms.value)
+
+    def __exit__(self, *exc):
+        events, self._events = self._events, []
+        for e in events:
+            hip_call("mde_rt_event_destroy", e)
+        return False
 
 
 def _do_inference_base(inputs, outputs, stream, execute_async_func, timer=None):

@@ -5,8 +5,8 @@
 //
 // Contract: include/mde.h, mde_op_cloud_view (pointcloud.py:render_np is the numpy restatement the tests
 // hold these kernels to, the picture byte for byte and the view row bit for bit).  -ffp-contract=off for
-// the file (_build.PER_FILE) and the pragma below: every float32 and float64 operation rounds on its own,
-// as numpy's do; the unprojection is point_cloud.hip's, __f*_rn per step.
+// the file (_build.PER_FILE) and cloud_source.h's pragma: every float32 and float64 operation rounds on its own,
+// as numpy's do; the grid, the camera and the unprojection are cloud_source.h's, shared with point_cloud.hip.
 //
 // Structure (ws: z-buffer | quantile rows | workgroup counts | planes | quantile scratch), all on the stream:
 //   cv_planes     X, Y, Z of every sample as three float32 planes, NaN where the sample is invalid
@@ -30,13 +30,7 @@
 // decreases, so a value read earlier (even a stale one from a cache) is never below the final one: a
 // sample that is skipped would have lost anyway, and the result is the same.
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "mde_ops.h"
-
-#pragma clang fp contract(off)
+#include "cloud_source.h"
 
 namespace mde {
 namespace {
@@ -47,35 +41,20 @@ constexpr unsigned long long kEmpty = ~0ull;
 
 static_assert(kThreads % 64 == 0, "ballots below are over wave64");
 
-struct Geom {
-  int h, w, step, hs, ws;  // hs * ws < 2^30 - 128 (the ABI wrapper)
-};
-
-struct Camera {
-  const unsigned char* photo;
-  const float* f_px_dev;
-  int pitch, swap_rb;
-  float fx, fy, cx, cy;
-};
-
 struct Trig {
   double cos_a, sin_a, cos_e, sin_e;
 };
 
 __device__ __forceinline__ bool finite32(float x) { return __builtin_fabsf(x) < __builtin_inff(); }
 
-// sample s (< hs * ws) of image b: its pixel, X, Y, Z as mde_op_point_cloud computes them, and whether
-// the sample is drawn (the reference's subsample_cloud keep rule)
-__device__ __forceinline__ bool unproject(const float* __restrict__ img, const Geom& g, float fx, float fy, float cx,
-                                          float cy, unsigned s, int& v, int& u, float& X, float& Y, float& Z) {
-  const int i = (int)(s / (unsigned)g.ws), j = (int)(s - (unsigned)i * (unsigned)g.ws);
-  v = i * g.step;
-  u = j * g.step;
+// sample s of image b (img its depth map): X, Y, Z as mde_op_point_cloud computes them; whether the sample is
+// drawn (the reference's subsample_cloud keep rule), false past the grid's end
+__device__ __forceinline__ bool drawn(const float* __restrict__ img, const Geom& g, const Camera& cam, Focal f,
+                                      unsigned s, float& X, float& Y, float& Z) {
+  int v, u;
+  if (!sample_pixel(g, s, v, u)) return false;
   Z = img[(size_t)v * g.w + u];
-  const float xn = __fdiv_rn(__fsub_rn((float)u, cx), fx);
-  const float yn = __fdiv_rn(__fsub_rn((float)v, cy), fy);
-  X = __fmul_rn(xn, Z);
-  Y = __fmul_rn(yn, Z);
+  unproject_xy(cam, f, v, u, Z, X, Y);
   return finite32(X) && finite32(Y) && finite32(Z) && Z > 0.f;
 }
 
@@ -91,11 +70,8 @@ cv_planes(const float* __restrict__ depth, Geom g, Camera cam, float* __restrict
   const int b = (int)blockIdx.y;
   const unsigned n = (unsigned)(g.hs * g.ws), s = blockIdx.x * (unsigned)kThreads + threadIdx.x;
   if (s >= n) return;
-  float fx = cam.fx, fy = cam.fy;
-  if (cam.f_px_dev) fx = fy = cam.f_px_dev[b];
-  int v, u;
   float X, Y, Z;
-  const bool ok = unproject(depth + (size_t)b * g.h * g.w, g, fx, fy, cam.cx, cam.cy, s, v, u, X, Y, Z);
+  const bool ok = drawn(depth + (size_t)b * g.h * g.w, g, cam, cam.focal(b), s, X, Y, Z);
   const float nan = __builtin_nanf("");
   float* p = planes + (size_t)b * 3 * n;
   p[s] = ok ? X : nan;
@@ -111,11 +87,8 @@ cv_abs(const float* __restrict__ depth, Geom g, Camera cam, Trig t, const double
   const int b = (int)blockIdx.y;
   const unsigned n = (unsigned)(g.hs * g.ws), s = blockIdx.x * (unsigned)kThreads + threadIdx.x;
   if (s >= n) return;
-  float fx = cam.fx, fy = cam.fy;
-  if (cam.f_px_dev) fx = fy = cam.f_px_dev[b];
-  int v, u;
   float X, Y, Z;
-  const bool ok = unproject(depth + (size_t)b * g.h * g.w, g, fx, fy, cam.cx, cam.cy, s, v, u, X, Y, Z);
+  const bool ok = drawn(depth + (size_t)b * g.h * g.w, g, cam, cam.focal(b), s, X, Y, Z);
   float ax = __builtin_nanf(""), ay = ax;
   if (ok) {
     const double* c = centre + (size_t)b * 3 * kRow;
@@ -174,11 +147,8 @@ cv_splat(const float* __restrict__ depth, Geom g, Camera cam, Trig t, const doub
   unsigned long long packed = kEmpty;
   unsigned pixel = 0;
   if (s < n) {
-    float fx = cam.fx, fy = cam.fy;
-    if (cam.f_px_dev) fx = fy = cam.f_px_dev[b];
-    int v, u;
     float X, Y, Z;
-    ok = unproject(depth + (size_t)b * g.h * g.w, g, fx, fy, cam.cx, cam.cy, s, v, u, X, Y, Z);
+    ok = drawn(depth + (size_t)b * g.h * g.w, g, cam, cam.focal(b), s, X, Y, Z);
     if (ok) {
       const double* vw = view + (size_t)b * kRow;
       const double scale = vw[5];
@@ -248,13 +218,9 @@ cv_resolve(const unsigned long long* __restrict__ zbuf, Geom g, Camera cam, unsi
   if (p != kEmpty) {
     r = gr = bl = 200;
     if (cam.photo) {
-      const unsigned s = (unsigned)(p & 0xffffffffull);
-      const int si = (int)(s / (unsigned)g.ws), sj = (int)(s - (unsigned)si * (unsigned)g.ws);
-      const unsigned char* px = cam.photo + ((size_t)b * g.h + (size_t)si * g.step) * cam.pitch + 3 * (size_t)sj * g.step;
-      const unsigned char c0 = px[0], c1 = px[1], c2 = px[2];
-      r = cam.swap_rb ? c2 : c0;
-      gr = c1;
-      bl = cam.swap_rb ? c0 : c2;
+      int v = 0, u = 0;
+      sample_pixel(g, (unsigned)(p & 0xffffffffull), v, u);  // the winner is a sample of the grid
+      photo_rgb(cam, g, b, v, u, r, gr, bl);
     }
   }
   unsigned char* o = out + ((size_t)b * pixels + i) * 3;
@@ -270,15 +236,15 @@ struct Layout {
 };
 
 Layout layout_of(int B, int h, int w, int step, int out_h, int out_w) {
-  const int hs = (h + step - 1) / step, ws = (w + step - 1) / step;
-  const size_t n = (size_t)hs * ws;
+  const Geom g = make_geom(h, w, step);
+  const size_t n = (size_t)g.hs * g.ws;
   Layout l;
   l.zbuf = 0;
   l.rows = l.zbuf + (size_t)B * out_h * out_w * sizeof(unsigned long long);
   l.counters = l.rows + (size_t)B * 4 * kRow * sizeof(double);  // three centre rows and one span row per image
   l.planes = l.counters + (size_t)B * ((n + kThreads - 1) / kThreads) * 2 * sizeof(unsigned);  // cv_splat's slots
   l.quant = l.planes + round8((size_t)B * 3 * n * sizeof(float));
-  l.total = l.quant + round8(depth_quantiles_ws_bytes(3 * B, hs, ws));
+  l.total = l.quant + round8(depth_quantiles_ws_bytes(3 * B, g.hs, g.ws));
   return l;
 }
 
@@ -292,17 +258,15 @@ size_t cloud_view_ws_bytes(int B, int h, int w, int step, int out_h, int out_w) 
 // sizes, a sampled grid of 2^30 - 128 samples or more (two planes pooled in one quantile call), a picture
 // of 2^31 - 256 pixels or more, batch > 21845 (three planes per image on grid.y), a short or misaligned
 // workspace, misaligned view rows, a missing focal length and non-finite trig values.
-hipError_t launch_cloud_view(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
-                             int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, double cos_a,
-                             double sin_a, double cos_e, double sin_e, const double* view_in, const int bg_rgb[3],
-                             int out_swap_rb, unsigned char* out, int out_h, int out_w, double* view_out, void* ws,
-                             hipStream_t st) {
-  Geom g;
-  g.h = h, g.w = w, g.step = step;
-  g.hs = (h + step - 1) / step, g.ws = (w + step - 1) / step;
-  const Camera cam = {photo, f_px_dev, pitch, swap_rb, fx, fy, cx, cy};
+hipError_t launch_cloud_view(const CloudSource& src, double cos_a, double sin_a, double cos_e, double sin_e,
+                             const double* view_in, const int bg_rgb[3], int out_swap_rb, unsigned char* out,
+                             int out_h, int out_w, double* view_out, void* ws, hipStream_t st) {
+  const Geom g = make_geom(src.h, src.w, src.step);
+  const Camera cam = make_camera(src);
   const Trig t = {cos_a, sin_a, cos_e, sin_e};
-  const Layout l = layout_of(B, h, w, step, out_h, out_w);
+  const float* depth = src.depth;
+  const int B = src.B;
+  const Layout l = layout_of(B, src.h, src.w, src.step, out_h, out_w);
   char* base = static_cast<char*>(ws);
   unsigned long long* zbuf = reinterpret_cast<unsigned long long*>(base + l.zbuf);
   double* centre = reinterpret_cast<double*>(base + l.rows);

@@ -1,9 +1,7 @@
-// What point_cloud.hip and depth_mesh.hip share: the sampled grid, the PLY vertex record and its
-// unprojection, a sample's rank among the kept ones of its tile, the scan of the tiles' counts and the
-// LDS-staged store of a tile's odd-sized records.  Device code in a header: each of the two files gets
-// its own copy in its own anonymous namespace, and both are built with -ffp-contract=off
-// (_build.PER_FILE); the pragma below says the same for the unprojection here and for the rest of the
-// including file.
+// What point_cloud.hip and depth_mesh.hip share on top of cloud_source.h (the sampled grid, the camera,
+// the unprojection and the fp-contract story): the PLY vertex record, a sample's rank among the kept
+// ones of its tile, the scan of the tiles' counts and the LDS-staged store of a tile's odd-sized records.
+// Device code in a header: each of the two files gets its own copy in its own anonymous namespace.
 //
 // Tiles.  A workgroup of 256 threads owns kTile = 1024 consecutive samples of one image; thread t takes
 // samples t, t + 256, t + 512, t + 768 of the tile, so a wave reads 64 consecutive elements per load.  A
@@ -19,11 +17,7 @@
 // exactly its own bytes.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#pragma clang fp contract(off)
+#include "cloud_source.h"
 
 namespace mde {
 namespace {
@@ -45,47 +39,20 @@ struct __attribute__((packed)) Rec15 {
 };
 static_assert(sizeof(Rec12) == 12 && sizeof(Rec15) == 15, "PLY vertex records are tightly packed");
 
-struct Geom {
-  int h, w, step, hs, ws;  // hs * ws < 2^31 - 256 (the ABI wrappers)
-};
-
-inline Geom make_geom(int h, int w, int step) {
-  Geom g;
-  g.h = h, g.w = w, g.step = step;
-  g.hs = (h + step - 1) / step, g.ws = (w + step - 1) / step;
-  return g;
-}
-
 // the one statement of validity: every kernel must agree on every sample
 __device__ __forceinline__ bool keep(float z, float z_lo, float z_hi) { return z == z && z >= z_lo && z <= z_hi; }
 
-// sample s of image b -> its pixel; returns false past the grid's end
-// (s is unsigned: the last tile's sample indices run up to 1023 past hs * ws, past INT_MAX for the
-// largest grids the wrappers let through)
-__device__ __forceinline__ bool sample_pixel(const Geom& g, unsigned s, int& v, int& u) {
-  if (s >= (unsigned)(g.hs * g.ws)) return false;
-  const int i = (int)(s / (unsigned)g.ws), j = (int)(s - (unsigned)i * (unsigned)g.ws);
-  v = i * g.step;
-  u = j * g.step;
-  return true;
-}
-
-// the record of pixel (v, u) at depth z: each float32 step rounded on its own
+// the record of pixel (v, u) of image b at depth z
 template <typename Rec, bool COLOUR>
-__device__ __forceinline__ Rec unproject(const Geom& g, int b, int v, int u, float z, float fx, float fy, float cx,
-                                         float cy, const unsigned char* __restrict__ photo, int pitch, int swap_rb) {
+__device__ __forceinline__ Rec unproject(const Geom& g, const Camera& cam, Focal f, int b, int v, int u, float z) {
   Rec r;
-  const float xn = __fdiv_rn(__fsub_rn((float)u, cx), fx);
-  const float yn = __fdiv_rn(__fsub_rn((float)v, cy), fy);
-  r.x = __fmul_rn(xn, z);
-  r.y = __fmul_rn(yn, z);
-  r.z = z;
+  float X, Y;  // a packed field does not bind to a reference
+  unproject_xy(cam, f, v, u, z, X, Y);
+  r.x = X, r.y = Y, r.z = z;
   if constexpr (COLOUR) {
-    const unsigned char* px = photo + ((size_t)b * g.h + v) * pitch + 3 * (size_t)u;
-    const unsigned char c0 = px[0], c1 = px[1], c2 = px[2];
-    r.r = swap_rb ? c2 : c0;
-    r.g = c1;
-    r.b = swap_rb ? c0 : c2;
+    unsigned char red, green, blue;
+    photo_rgb(cam, g, b, v, u, red, green, blue);
+    r.r = red, r.g = green, r.b = blue;
   }
   return r;
 }

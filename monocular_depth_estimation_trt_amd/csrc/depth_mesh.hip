@@ -16,7 +16,7 @@
 //   vertex      = faces ? one of its up to four quads is kept : clean
 //
 // Rounding discipline: as point_cloud.hip -- __f*_rn per step, -ffp-contract=off for the file
-// (_build.PER_FILE) and the pragma below.
+// (_build.PER_FILE) and cloud_source.h's pragma.
 //
 // Structure.  Six launches on the stream (four without faces), none of which waits on memory another
 // workgroup writes: the order between them is the stream's.
@@ -43,8 +43,6 @@
 
 #include "compact_store.h"
 #include "mde_ops.h"
-
-#pragma clang fp contract(off)
 
 namespace mde {
 namespace {
@@ -183,7 +181,9 @@ mesh_vertex_kernel(const float* __restrict__ depth, Geom g, const unsigned char*
   __shared__ int s_cnt[kSegs];
   const int b = (int)blockIdx.y, t = (int)threadIdx.x;
   const int plane = g.hs * g.ws;
-  if (f_px_dev) fx = fy = f_px_dev[b];
+  // loose arguments, not a Camera: see pc_write_kernel (point_cloud.hip)
+  const Camera cam = {photo, f_px_dev, pitch, swap_rb, fx, fy, cx, cy};
+  const Focal f = cam.focal(b);
   const float* img = depth + (size_t)b * g.h * g.w;
   const unsigned char* fl = flags + (size_t)b * plane;
 
@@ -194,8 +194,7 @@ mesh_vertex_kernel(const float* __restrict__ depth, Geom g, const unsigned char*
     int v = 0, u = 0;
     const unsigned s = blockIdx.x * (unsigned)kTile + (unsigned)(p * kThreads + t);
     k[p] = sample_pixel(g, s, v, u) && (fl[s] & kVertex) != 0;
-    if (k[p])
-      r[p] = unproject<Rec, COLOUR>(g, b, v, u, img[(size_t)v * g.w + u], fx, fy, cx, cy, photo, pitch, swap_rb);
+    if (k[p]) r[p] = unproject<Rec, COLOUR>(g, cam, f, b, v, u, img[(size_t)v * g.w + u]);
   }
   int rank[kPasses];
   const int n = tile_ranks(k, rank, s_cnt);
@@ -263,11 +262,12 @@ size_t depth_mesh_ws_bytes(int B, int h, int w, int step) {
 // Checks nothing: the one caller, mde_op_depth_mesh in ops_abi.hip, has refused what
 // mde_op_point_cloud refuses, 2 * (hs - 1) * (ws - 1) of 2^31 - 256 or more with faces (int triangle
 // index), bad tolerances, short buffers and a ws that is not 4-byte aligned.
-hipError_t launch_depth_mesh(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
-                             int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, float z_lo,
-                             float z_hi, float edge_rtol, float edge_atol, int faces, void* vertices,
-                             int* vertex_counts, void* face_records, int* face_counts, void* ws, hipStream_t st) {
-  const Geom g = make_geom(h, w, step);
+hipError_t launch_depth_mesh(const CloudSource& src, float z_lo, float z_hi, float edge_rtol, float edge_atol,
+                             int faces, void* vertices, int* vertex_counts, void* face_records, int* face_counts,
+                             void* ws, hipStream_t st) {
+  const Geom g = make_geom(src.h, src.w, src.step);
+  const float* depth = src.depth;
+  const int B = src.B;
   const int plane = g.hs * g.ws, tiles = mesh_tiles(g);
   int* tile_v = static_cast<int*>(ws);
   int* tile_t = tile_v + (size_t)B * tiles;
@@ -283,12 +283,11 @@ hipError_t launch_depth_mesh(const float* depth, int B, int h, int w, int step, 
   if (faces)
     hipLaunchKernelGGL(tile_scan_kernel, dim3((unsigned)B), dim3(kScanThreads), 0, st, tile_t, tiles, face_counts);
   unsigned char* rec = static_cast<unsigned char*>(vertices);
-  if (photo)
-    hipLaunchKernelGGL(mesh_vertex_kernel<true>, grid, block, 0, st, depth, g, photo, pitch, swap_rb, f_px_dev, fx,
-                       fy, cx, cy, flags, rec, tile_v, index, tiles);
-  else
-    hipLaunchKernelGGL(mesh_vertex_kernel<false>, grid, block, 0, st, depth, g, photo, pitch, swap_rb, f_px_dev, fx,
-                       fy, cx, cy, flags, rec, tile_v, index, tiles);
+#define MESH_VERTEX(COLOUR)                                                                                       \
+  hipLaunchKernelGGL(mesh_vertex_kernel<COLOUR>, grid, block, 0, st, depth, g, src.photo, src.pitch, src.swap_rb, \
+                     src.f_px_dev, src.fx, src.fy, src.cx, src.cy, flags, rec, tile_v, index, tiles)
+  if (src.photo) MESH_VERTEX(true); else MESH_VERTEX(false);
+#undef MESH_VERTEX
   if (faces)
     hipLaunchKernelGGL(mesh_face_kernel, grid, block, 0, st, g, flags, index, static_cast<unsigned char*>(face_records),
                        2LL * (g.hs - 1) * (g.ws - 1), tile_t, tiles);

@@ -226,15 +226,26 @@ hipError_t launch_dp_preprocess(const unsigned char* src, int B, int sh, int sw,
                                 const float* lut, float* dst, int oh, int ow, hipStream_t st);
 hipError_t launch_dp_postprocess(const float* inv, int B, int ih, int iw, const float* fov_deg, float f_px,
                                  float* f_px_out, float* out, int oh, int ow, hipStream_t st);
+// The cloud source of launch_point_cloud, launch_depth_mesh and launch_cloud_view: fp32 depth [B][h][w]
+// sampled at every step-th pixel on both axes, an optional photo [B][h][pitch] (3 bytes per pixel, its
+// channels reversed when swap_rb) and the pinhole camera -- fx = fy = f_px_dev[b] when f_px_dev is given,
+// else the host's fx, fy; cx, cy.  The fields are the mde_op_* arguments of the same names.
+struct CloudSource {
+  const float* depth;
+  int B, h, w, step;
+  const unsigned char* photo;
+  int pitch, swap_rb;
+  const float* f_px_dev;
+  float fx, fy, cx, cy;
+};
 // point_cloud.hip: pinhole unprojection of fp32 depth [B][h][w] (every step-th pixel on both axes) into
 // packed PLY vertex records (float x, y, z [+ uchar r, g, b from photo [B][h][pitch]]), organized or
 // compacted to z in [z_lo, z_hi]; counts int[B]; ws = point_cloud_ws_bytes() of scratch (compact only).
 // Enqueues one (organized) or three (compact) kernels, nothing else.  No argument checks here: the ABI
 // wrapper in ops_abi.hip holds the only copy of the limits
 size_t point_cloud_ws_bytes(int B, int h, int w, int step);
-hipError_t launch_point_cloud(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
-                              int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
-                              float z_lo, float z_hi, void* records, int* counts, void* ws, hipStream_t st);
+hipError_t launch_point_cloud(const CloudSource& src, int compact, float z_lo, float z_hi, void* records, int* counts,
+                              void* ws, hipStream_t st);
 // depth_mesh.hip: the same grid, camera and vertex records as launch_point_cloud, after the depth-edge
 // filter (include/mde.h, mde_op_depth_mesh): the vertices the kept quads use (faces != 0) or the clean
 // samples (faces == 0), compacted, and two 13-byte PLY face entries per kept quad; vertex_counts, face_counts
@@ -242,10 +253,9 @@ hipError_t launch_point_cloud(const float* depth, int B, int h, int w, int step,
 // faces), nothing else.  No argument checks here: the ABI wrapper in ops_abi.hip holds the only copy of
 // the limits
 size_t depth_mesh_ws_bytes(int B, int h, int w, int step);
-hipError_t launch_depth_mesh(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
-                             int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, float z_lo,
-                             float z_hi, float edge_rtol, float edge_atol, int faces, void* vertices,
-                             int* vertex_counts, void* face_records, int* face_counts, void* ws, hipStream_t st);
+hipError_t launch_depth_mesh(const CloudSource& src, float z_lo, float z_hi, float edge_rtol, float edge_atol,
+                             int faces, void* vertices, int* vertex_counts, void* face_records, int* face_counts,
+                             void* ws, hipStream_t st);
 // depth_eval.hip: fp32 prediction and ground truth [B][h][w] and a uint8 mask -> double out[B][16]
 // (include/mde.h, mde_op_depth_eval: fit status and parameters, the metrics, the orientation);
 // ws = depth_eval_ws_bytes() of 8-byte aligned scratch.  Enqueues four kernels, nothing else.  No
@@ -278,18 +288,16 @@ hipError_t launch_depth_quantiles(const float* map, int B, int h, int w, int pos
                                   int pooled, int sample_cap, const double* q_percent, int nq, double* out, void* ws,
                                   hipStream_t st);
 // cloud_view.hip: an orthographic, z-buffered picture uint8 [B][out_h][out_w][3] of the cloud that
-// launch_point_cloud would pack (the same depth, photo and camera arguments), seen from the angles whose
+// launch_point_cloud would pack (the same CloudSource), seen from the angles whose
 // cosines and sines the caller gives (include/mde.h, mde_op_cloud_view); view_out double[B][8]: the
 // counts, the centre, the span and the scale; view_in non-null: a fixed camera, no selection.  ws =
 // cloud_view_ws_bytes() of 8-byte aligned scratch.  Enqueues kernels (and launch_depth_quantiles, 1 + B
 // times, without view_in), nothing else.  No argument checks here: the ABI wrapper in ops_abi.hip holds
 // the only copy of the limits
 size_t cloud_view_ws_bytes(int B, int h, int w, int step, int out_h, int out_w);
-hipError_t launch_cloud_view(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
-                             int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, double cos_a,
-                             double sin_a, double cos_e, double sin_e, const double* view_in, const int bg_rgb[3],
-                             int out_swap_rb, unsigned char* out, int out_h, int out_w, double* view_out, void* ws,
-                             hipStream_t st);
+hipError_t launch_cloud_view(const CloudSource& src, double cos_a, double sin_a, double cos_e, double sin_e,
+                             const double* view_in, const int bg_rgb[3], int out_swap_rb, unsigned char* out,
+                             int out_h, int out_w, double* view_out, void* ws, hipStream_t st);
 // preprocess_cubic.hip: cv2's uint8 INTER_CUBIC of [B][sh][pitch] 3-channel rows seen through a virtual
 // constant border of pad_* pixels (include/mde.h, mde_op_resize_cubic_u8; pad_rgb in output channel
 // order); lut == nullptr: dst uint8 NHWC [B][oh][ow][3]; else dst float NCHW [B][3][oh][ow] =

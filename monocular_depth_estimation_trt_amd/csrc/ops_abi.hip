@@ -124,6 +124,22 @@ const char* point_cloud_geometry_error(int batch, int h, int w, int step, long l
   if (batch > 65535) return "batch > 65535";
   return nullptr;
 }
+
+// why a cloud source is unusable, in the order the three ops report it, else nullptr and the sampled
+// plane's size: a null depth, the geometry, the photo's pitch, the focal length, the centre
+const char* cloud_source_error(const CloudSource& s, long long* plane) {
+  if (!s.depth) return "null pointer";
+  if (const char* why = point_cloud_geometry_error(s.B, s.h, s.w, s.step, plane)) return why;
+  if (s.photo && s.pitch < 3 * (long long)s.w) return "pitch < 3 * w";
+  if (!s.f_px_dev && !(s.fx > 0.f && s.fy > 0.f)) return "f_px_dev is null and fx <= 0 or fy <= 0";
+  if (!(s.cx == s.cx && s.cy == s.cy)) return "cx or cy is NaN";
+  return nullptr;
+}
+
+// batch <= 65535, plane < 2^31, a record of 15 bytes at most: no overflow in 64 bits
+unsigned long long vertex_bytes(const CloudSource& s, long long plane) {
+  return (unsigned long long)s.B * plane * (s.photo ? 15 : 12);
+}
 }  // namespace
 
 size_t mde_op_point_cloud_ws_bytes(int batch, int h, int w, int step) {
@@ -136,24 +152,17 @@ int mde_op_point_cloud(const float* depth, int batch, int h, int w, int step, co
                        int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
                        float z_lo, float z_hi, void* records, size_t records_bytes, int* counts, void* ws,
                        size_t ws_bytes, void* st) {
+  const CloudSource src = {depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy};
   long long plane = 0;
-  const char* why = (!depth || !records || !counts) ? "null pointer"
-                                                    : point_cloud_geometry_error(batch, h, w, step, &plane);
-  if (!why && photo && pitch < 3 * (long long)w) why = "pitch < 3 * w";
-  if (!why && !f_px_dev && !(fx > 0.f && fy > 0.f)) why = "f_px_dev is null and fx <= 0 or fy <= 0";
-  if (!why && !(cx == cx && cy == cy)) why = "cx or cy is NaN";
-  // batch <= 65535, plane < 2^31, rec <= 15: no overflow in 64 bits
-  if (!why && records_bytes < (unsigned long long)batch * plane * (photo ? 15 : 12))
-    why = "records_bytes < batch * hs * ws * record size";
+  const char* why = (!records || !counts) ? "null pointer" : cloud_source_error(src, &plane);
+  if (!why && records_bytes < vertex_bytes(src, plane)) why = "records_bytes < batch * hs * ws * record size";
   if (!why && compact) {
     if (!(z_lo <= z_hi)) why = "z_lo > z_hi (or NaN)";
     else if (!ws || ws_bytes < point_cloud_ws_bytes(batch, h, w, step))
       why = "compact mode needs ws of mde_op_point_cloud_ws_bytes()";
   }
   if (why) return fail(MDE_ERR_ARG, std::string("mde_op_point_cloud: ") + why);
-  OP_RET(launch_point_cloud(depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy, compact, z_lo,
-                            z_hi, records, counts, ws, (hipStream_t)st),
-         "mde_op_point_cloud");
+  OP_RET(launch_point_cloud(src, compact, z_lo, z_hi, records, counts, ws, (hipStream_t)st), "mde_op_point_cloud");
 }
 
 size_t mde_op_depth_mesh_ws_bytes(int batch, int h, int w, int step) {
@@ -167,14 +176,10 @@ int mde_op_depth_mesh(const float* depth, int batch, int h, int w, int step, con
                       float z_hi, float edge_rtol, float edge_atol, int faces, void* vertices, size_t vertices_bytes,
                       int* vertex_counts, void* face_records, size_t faces_bytes, int* face_counts, void* ws,
                       size_t ws_bytes, void* st) {
+  const CloudSource src = {depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy};
   long long plane = 0;
-  const char* why = (!depth || !vertices || !vertex_counts) ? "null pointer"
-                                                            : point_cloud_geometry_error(batch, h, w, step, &plane);
-  if (!why && photo && pitch < 3 * (long long)w) why = "pitch < 3 * w";
-  if (!why && !f_px_dev && !(fx > 0.f && fy > 0.f)) why = "f_px_dev is null and fx <= 0 or fy <= 0";
-  if (!why && !(cx == cx && cy == cy)) why = "cx or cy is NaN";
-  if (!why && vertices_bytes < (unsigned long long)batch * plane * (photo ? 15 : 12))
-    why = "vertices_bytes < batch * hs * ws * record size";
+  const char* why = (!vertices || !vertex_counts) ? "null pointer" : cloud_source_error(src, &plane);
+  if (!why && vertices_bytes < vertex_bytes(src, plane)) why = "vertices_bytes < batch * hs * ws * record size";
   if (!why && !(z_lo <= z_hi)) why = "z_lo > z_hi (or NaN)";
   if (!why && !(edge_rtol >= 0.f && edge_atol >= 0.f)) why = "edge_rtol or edge_atol is negative or NaN";
   if (!why && faces) {
@@ -189,9 +194,8 @@ int mde_op_depth_mesh(const float* depth, int batch, int h, int w, int step, con
     why = "needs ws of mde_op_depth_mesh_ws_bytes()";
   if (!why && (reinterpret_cast<uintptr_t>(ws) & 3)) why = "ws must be 4-byte aligned";
   if (why) return fail(MDE_ERR_ARG, std::string("mde_op_depth_mesh: ") + why);
-  OP_RET(launch_depth_mesh(depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy, z_lo, z_hi,
-                           edge_rtol, edge_atol, faces, vertices, vertex_counts, face_records, face_counts, ws,
-                           (hipStream_t)st),
+  OP_RET(launch_depth_mesh(src, z_lo, z_hi, edge_rtol, edge_atol, faces, vertices, vertex_counts, face_records,
+                           face_counts, ws, (hipStream_t)st),
          "mde_op_depth_mesh");
 }
 
@@ -219,12 +223,14 @@ int mde_op_cloud_view(const float* depth, int batch, int h, int w, int step, con
                       double sin_a, double cos_e, double sin_e, const double* view_in, const int* bg_rgb,
                       int out_swap_rb, unsigned char* out_u8, int out_h, int out_w, double* view_out, void* ws,
                       size_t ws_bytes, void* st) {
+  const CloudSource src = {depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy};
+  long long plane = 0;
+  // the view's stricter limits speak after the shared geometry and before the rest of the source: the
+  // geometry is judged here first and passes again inside cloud_source_error
   const char* why = (!depth || !out_u8 || !view_out || !bg_rgb)
                         ? "null pointer"
                         : cloud_view_geometry_error(batch, h, w, step, out_h, out_w);
-  if (!why && photo && pitch < 3 * (long long)w) why = "pitch < 3 * w";
-  if (!why && !f_px_dev && !(fx > 0.f && fy > 0.f)) why = "f_px_dev is null and fx <= 0 or fy <= 0";
-  if (!why && !(cx == cx && cy == cy)) why = "cx or cy is NaN";
+  if (!why) why = cloud_source_error(src, &plane);
   for (double t : {cos_a, sin_a, cos_e, sin_e})
     if (!why && !(t - t == 0.0)) why = "a NaN or infinite trig value";
   for (int c = 0; !why && c < 3; ++c)
@@ -235,9 +241,8 @@ int mde_op_cloud_view(const float* depth, int batch, int h, int w, int step, con
                 reinterpret_cast<uintptr_t>(view_out)) & 7))
     why = "ws, view_in and view_out must be 8-byte aligned";
   if (why) return fail(MDE_ERR_ARG, std::string("mde_op_cloud_view: ") + why);
-  OP_RET(launch_cloud_view(depth, batch, h, w, step, photo, pitch, swap_rb, f_px_dev, fx, fy, cx, cy, cos_a, sin_a,
-                           cos_e, sin_e, view_in, bg_rgb, out_swap_rb != 0, out_u8, out_h, out_w, view_out, ws,
-                           (hipStream_t)st),
+  OP_RET(launch_cloud_view(src, cos_a, sin_a, cos_e, sin_e, view_in, bg_rgb, out_swap_rb != 0, out_u8, out_h, out_w,
+                           view_out, ws, (hipStream_t)st),
          "mde_op_cloud_view");
 }
 

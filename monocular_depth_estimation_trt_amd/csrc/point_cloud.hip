@@ -23,7 +23,7 @@
 //            records are not written
 //
 // Rounding discipline: as in depth_pro_photo.hip -- __f*_rn per step, -ffp-contract=off for the
-// file (_build.PER_FILE) and the pragma below, no fast-math flag in the build.
+// file (_build.PER_FILE) and cloud_source.h's pragma, no fast-math flag in the build.
 //
 // Structure.  Tiles of 1024 samples, a sample's rank within its tile, the scan of the tiles' counts and
 // the LDS-staged store are compact_store.h's (shared with depth_mesh.hip).
@@ -46,8 +46,6 @@
 
 #include "compact_store.h"
 #include "mde_ops.h"
-
-#pragma clang fp contract(off)
 
 namespace mde {
 namespace {
@@ -88,7 +86,10 @@ pc_write_kernel(const float* __restrict__ depth, Geom g, const unsigned char* __
   __shared__ int s_cnt[kSegs];
   const int b = (int)blockIdx.y, t = (int)threadIdx.x;
   const int plane = g.hs * g.ws;
-  if (f_px_dev) fx = fy = f_px_dev[b];
+  // the camera arrives as loose arguments: a struct argument's fields are fetched from the kernarg segment
+  // where they are first used, which put a second, dependent fetch in front of the first sample
+  const Camera cam = {photo, f_px_dev, pitch, swap_rb, fx, fy, cx, cy};
+  const Focal f = cam.focal(b);
   const float* img = depth + (size_t)b * g.h * g.w;
 
   Rec r[kPasses];
@@ -102,7 +103,7 @@ pc_write_kernel(const float* __restrict__ depth, Geom g, const unsigned char* __
       z = img[(size_t)v * g.w + u];
       if (COMPACT) k[p] = keep(z, z_lo, z_hi);
     }
-    if (k[p]) r[p] = unproject<Rec, COLOUR>(g, b, v, u, z, fx, fy, cx, cy, photo, pitch, swap_rb);
+    if (k[p]) r[p] = unproject<Rec, COLOUR>(g, cam, f, b, v, u, z);
   }
   int rank[kPasses];
   const int n = tile_ranks(k, rank, s_cnt);  // records of this tile
@@ -132,24 +133,25 @@ size_t point_cloud_ws_bytes(int B, int h, int w, int step) {
 // Checks nothing: the one caller, mde_op_point_cloud in ops_abi.hip, has refused null pointers,
 // non-positive sizes, a sampled grid of 2^31 - 256 samples or more (int sample index), batch >
 // 65535 (grid.y), a short records buffer or workspace and a missing focal length.
-hipError_t launch_point_cloud(const float* depth, int B, int h, int w, int step, const unsigned char* photo, int pitch,
-                              int swap_rb, const float* f_px_dev, float fx, float fy, float cx, float cy, int compact,
-                              float z_lo, float z_hi, void* records, int* counts, void* ws, hipStream_t st) {
-  const Geom g = make_geom(h, w, step);
-  const int tiles = point_cloud_tiles(h, w, step);
+hipError_t launch_point_cloud(const CloudSource& src, int compact, float z_lo, float z_hi, void* records, int* counts,
+                              void* ws, hipStream_t st) {
+  const Geom g = make_geom(src.h, src.w, src.step);
+  const float* depth = src.depth;
+  const int B = src.B, tiles = point_cloud_tiles(src.h, src.w, src.step);
   const dim3 grid((unsigned)tiles, (unsigned)B), block(kThreads);
   int* tile_count = static_cast<int*>(ws);
   unsigned char* rec = static_cast<unsigned char*>(records);
 #define PC_WRITE(COMPACT, COLOUR)                                                                                  \
-  hipLaunchKernelGGL((pc_write_kernel<COMPACT, COLOUR>), grid, block, 0, st, depth, g, photo, pitch, swap_rb,      \
-                     f_px_dev, fx, fy, cx, cy, z_lo, z_hi, rec, tile_count, counts, tiles)
+  hipLaunchKernelGGL((pc_write_kernel<COMPACT, COLOUR>), grid, block, 0, st, depth, g, src.photo, src.pitch,       \
+                     src.swap_rb, src.f_px_dev, src.fx, src.fy, src.cx, src.cy, z_lo, z_hi, rec, tile_count,       \
+                     counts, tiles)
   if (!compact) {
-    if (photo) PC_WRITE(false, true); else PC_WRITE(false, false);
+    if (src.photo) PC_WRITE(false, true); else PC_WRITE(false, false);
     return hipGetLastError();
   }
   hipLaunchKernelGGL(pc_count_kernel, grid, block, 0, st, depth, g, z_lo, z_hi, tile_count, tiles);
   hipLaunchKernelGGL(tile_scan_kernel, dim3((unsigned)B), dim3(kScanThreads), 0, st, tile_count, tiles, counts);
-  if (photo) PC_WRITE(true, true); else PC_WRITE(true, false);
+  if (src.photo) PC_WRITE(true, true); else PC_WRITE(true, false);
 #undef PC_WRITE
   return hipGetLastError();
 }

@@ -21,7 +21,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _lib
-from .common_runtime import HostDeviceMem, stream_synchronize
+from .common_runtime import EventPair, HostDeviceMem, stream_synchronize
 
 POLICIES = ("none", "scale", "scale_shift")
 OUT_SLOTS = 16
@@ -368,26 +368,15 @@ def device_score(d_pred: int, h: int, w: int, stream: int, gt, mask, policy, pre
     """What the model drivers' --gt does: DeviceEval on one device map [h][w]
     at `d_pred`.  Returns (ms of the kernels + the 128-byte D2H between two
     hipEvents on `stream`, the result dict)."""
-    s = C.c_void_p(int(stream or 0))
-    ev = [C.c_void_p(), C.c_void_p()]
-    try:
-        for e in ev:
-            _lib.call("mde_rt_event_create", C.byref(e))
-        with DeviceEval(1, h, w) as de:
-            de.upload_gt(gt, mask, stream)
-            _lib.call("mde_rt_event_record", ev[0], s)
+    with DeviceEval(1, h, w) as de:
+        de.upload_gt(gt, mask, stream)
+        with EventPair(stream) as ev:
             de.enqueue(d_pred, stream, policy, pred_is_inverse=pred_is_inverse,
                        fit_finite_only=policy == "scale", max_depth=max_depth)
             de.download(stream)
-            _lib.call("mde_rt_event_record", ev[1], s)
+            ev.stop()
             stream_synchronize(stream)
-            ms = C.c_float()
-            _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
-            return float(ms.value), de.result()[0]
-    finally:
-        for e in ev:
-            if e:
-                _lib.call("mde_rt_event_destroy", e)
+            return ev.ms(), de.result()[0]
 
 
 def format_score(r: dict) -> str:

@@ -33,28 +33,14 @@ without it a synthetic image of the spec's input domain is used.  The
 post-process runs on the device (postprocess.DevicePostprocess) unless
 `--host-postprocess` asks for the reference's torch-CPU version.
 
-`--ply PATH` writes the point cloud of the metric depth map at the source size
-(the reference's models/depth_pro/onnx2trt_pointcloud.py:172-184 tail, which
-its docs/model_contracts.md allows for every "metric depth + focal length"
-model), on the device (pointcloud.DevicePointCloud) from the map the device
-post-process left there, coloured from the `--image` photo, depths outside this
-driver's clamp [1e-3, 1e3] dropped.  There is no FOV head: `--f-px` (focal
-length in pixels at the source size) is required.  Relative models (the
-relative checkpoints, depth_anything_ac, distill_any_depth) are refused:
-relative depth is not turned into metres.
-
-`--mesh PATH` is the reference's models/metric_anything/demo_pointcloud.py:
-142-149 under the same conditions as `--ply`: samples on a depth edge (3x3
-spread of depth above `--edge-rtol`, default 0.1, times the depth, or above
-`--edge-atol`) are dropped, the surviving 2x2 blocks become two triangles each
-and the mesh is packed on the device (pointcloud.DeviceMesh) as a binary PLY
-with vertices and faces.  `--ply-edge-rtol R` gives `--ply`'s cloud the same
-edge filter, without faces.
-
-`--cloud-view PATH` draws that cloud instead of packing it: the reference's
-core/viz.py:render_points (demo.py:cloud_figure), an orthographic, z-buffered
-picture seen from above-left, on the device (pointcloud.DeviceCloudView) under
-the same conditions as `--ply`; only the picture comes back.
+`--ply`, `--mesh` and `--cloud-view` are pointcloud.py's one stage for the
+cloud outputs, described there (the reference's docs/model_contracts.md allows
+them for every "metric depth + focal length" model).  Here they run on the map
+the device post-process left on the device, coloured from the `--image` photo,
+depths outside this driver's clamp [1e-3, 1e3] dropped.  There is no FOV head:
+`--f-px` (focal length in pixels at the source size) is required.  Relative
+models (the relative checkpoints, depth_anything_ac, distill_any_depth) are
+refused: relative depth is not turned into metres.
 
 `--gt DEPTH.npy --gt-mask MASK.npy` scores the map against measured ground
 truth of the same size (the reference's tools/evaluate_gt.py:555-583 over its
@@ -88,8 +74,8 @@ from monocular_depth_estimation_trt_amd import pointcloud
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
                                                            resize_linear_u8)
-from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
-                                                               stream_synchronize)
+from monocular_depth_estimation_trt_amd.common_runtime import (EventPair, allocate_buffers, do_inference,
+                                                               free_buffers, hip_call, stream_synchronize)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -121,33 +107,21 @@ def build_parser(model="depth_anything_v2", mc=None):
     ap.add_argument("--out-dir", default=os.path.join(os.getcwd(), "reports", "bench"))
     ap.add_argument("--input-format", choices=("float32_nchw", "uint8_nhwc"), default="float32_nchw")
     ap.add_argument("--host-postprocess", action="store_true")
-    ap.add_argument("--ply", default="", metavar="PATH",
-                    help="write the point cloud (binary PLY; colours from --image) of the metric depth; needs --f-px")
-    ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
     ap.add_argument("--f-px", type=float, default=None,
                     help="with --ply / --mesh / --cloud-view: focal length in pixels at the source size")
-    pointcloud.add_mesh_arguments(ap)
-    pointcloud.add_cloud_view_arguments(ap)
+    pointcloud.add_cloud_arguments(ap, needs_f_px=True)
     evaluate.add_gt_arguments(ap)
     visualize.add_color_arguments(ap)
     return ap
 
 
-NOT_METRIC = "--ply needs a metric model: relative depth is not turned into metres"
-
-
-def _check_ply(a, mc, opt="--ply"):
-    """--ply's (and --mesh's and --cloud-view's) conditions that can be answered before an engine is built."""
-    if a.f_px is None or not a.f_px > 0:
-        raise SystemExit(f"{opt} needs --f-px (a positive focal length in pixels): this model predicts none")
-    if opt == "--ply" and a.ply_step < 1:
-        raise SystemExit("--ply-step must be positive")
-    fields = a.source.split(":")
-    if mc["depth_type"] != "metric" or (fields[0] == "synthetic" and len(fields) > 2 and fields[2] == "relative"):
-        raise SystemExit(NOT_METRIC.replace("--ply", opt))
-    if a.host_postprocess or mc["postprocess"] == "none":
-        raise SystemExit(f"{opt} runs on the device post-process's depth map: not with --host-postprocess or a model "
-                         "without a post-process")
+def _check_cloud(a, mc, metric):
+    """pointcloud.check_cloud_arguments with what this driver knows: no FOV
+    head, and no device map under --host-postprocess or without a post-process."""
+    no_map = a.host_postprocess or mc["postprocess"] == "none"
+    pointcloud.check_cloud_arguments(
+        a, needs_f_px=True, metric=metric,
+        no_device_map="not with --host-postprocess or a model without a post-process" if no_map else "")
 
 
 def _device_preprocess(img, model, input_hw, input_format, mem, stream):
@@ -155,23 +129,14 @@ def _device_preprocess(img, model, input_hw, input_format, mem, stream):
     hipEvents (H2D of the frame + the kernel); the pinned side of the binding
     gets the same bytes back, so the timed loop's upload is a no-op in value."""
     import ctypes as C
-    ev = [C.c_void_p(), C.c_void_p()]
-    for e in ev:
-        hip_call("mde_rt_event_create", C.byref(e))
-    try:
-        with DevicePreprocess(img.shape[0], img.shape[1], *input_hw, model, output=input_format) as pre:
-            hip_call("mde_rt_event_record", ev[0], C.c_void_p(stream))
-            pre.run(img, mem.device, stream)
-            hip_call("mde_rt_event_record", ev[1], C.c_void_p(stream))
-            hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
-                     mem.nbytes, C.c_void_p(stream))
-            stream_synchronize(stream)
-        ms = C.c_float()
-        hip_call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
-    finally:
-        for e in ev:
-            hip_call("mde_rt_event_destroy", e)
-    return float(ms.value)
+    with DevicePreprocess(img.shape[0], img.shape[1], *input_hw, model, output=input_format) as pre, \
+            EventPair(stream) as ev:
+        pre.run(img, mem.device, stream)
+        ev.stop()
+        hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
+                 mem.nbytes, C.c_void_p(stream))
+        stream_synchronize(stream)
+        return ev.ms()
 
 
 def main(argv=None, model="depth_anything_v2"):
@@ -184,14 +149,9 @@ def main(argv=None, model="depth_anything_v2"):
         raise SystemExit("--image and --input are exclusive")
     if a.host_preprocess and not a.image:
         raise SystemExit("--host-preprocess needs --image")
-    if a.ply:
-        _check_ply(a, mc)
-    if a.mesh:
-        _check_ply(a, mc, "--mesh")
-    pointcloud.check_mesh_arguments(a)
-    if a.cloud_view:
-        _check_ply(a, mc, "--cloud-view")
-        pointcloud.check_cloud_view_arguments(a)
+    fields = a.source.split(":")
+    _check_cloud(a, mc, metric=mc["depth_type"] == "metric" and
+                 not (fields[0] == "synthetic" and len(fields) > 2 and fields[2] == "relative"))
     gt_policy = evaluate.check_gt_arguments(a, model_spec, device_map=not a.host_postprocess)
     visualize.check_color_arguments(a, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
@@ -199,12 +159,7 @@ def main(argv=None, model="depth_anything_v2"):
         a.src_hw = list(img.shape[:2]) if img is not None else [2268, 3024]
     gt_hw = (input_h, input_w) if mc["postprocess"] == "none" else tuple(a.src_hw)  # the size of the scored map
     gt_maps = evaluate.load_gt_arguments(a, gt_hw) if gt_policy else None
-    if a.ply and img is not None and tuple(a.src_hw) != img.shape[:2]:
-        raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
-    if a.mesh and img is not None and tuple(a.src_hw) != img.shape[:2]:
-        raise SystemExit("--mesh takes its colours from the --image photo: --src-hw must be the photo's size")
-    if a.cloud_view and img is not None and tuple(a.src_hw) != img.shape[:2]:
-        raise SystemExit("--cloud-view takes its colours from the --image photo: --src-hw must be the photo's size")
+    pointcloud.check_photo_size(a, img, a.src_hw)
     if u8 and a.engine.endswith("_fp16.mdeng"):
         a.engine = a.engine[:-len("_fp16.mdeng")] + "_u8_fp16.mdeng"
     if img is not None and a.host_preprocess:
@@ -226,12 +181,7 @@ def main(argv=None, model="depth_anything_v2"):
                            max_depth=mc["max_depth"], input_hw=(input_h, input_w),
                            input_format=a.input_format) as engine, \
             engine.create_execution_context() as context:
-        if a.ply and not engine.info.metric:
-            raise SystemExit(NOT_METRIC)
-        if a.mesh and not engine.info.metric:
-            raise SystemExit(NOT_METRIC.replace("--ply", "--mesh"))
-        if a.cloud_view and not engine.info.metric:
-            raise SystemExit(NOT_METRIC.replace("--ply", "--cloud-view"))
+        _check_cloud(a, mc, metric=engine.info.metric)
         inputs, outputs, bindings, stream = allocate_buffers(engine, output_shape, profile_idx=0)
         if x is None:
             ms = _device_preprocess(img, model, (input_h, input_w), a.input_format, inputs[0], stream)
@@ -255,16 +205,9 @@ def main(argv=None, model="depth_anything_v2"):
         else:  # the engine's output is still in outputs[0].device
             with DevicePostprocess(1, input_h, input_w, *a.src_hw) as pp:
                 depth = pp.run(outputs[0].device, stream)[0].copy()
-                if a.ply:  # the clamped map is still in pp.mem.device
-                    ms, n = pointcloud.driver_ply(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px,
-                                                  z_lo=1e-3, z_hi=1e3)
-                    print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {a.src_hw[0]}x{a.src_hw[1]} step "
-                          f"{a.ply_step} -> {a.ply} : {ms:0.3f} ms, {n} points")
-                if a.mesh:
-                    pointcloud.driver_mesh(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px, z_lo=1e-3,
-                                           z_hi=1e3)
-                if a.cloud_view:
-                    pointcloud.driver_cloud_view(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px)
+                # the clamped map is still in pp.mem.device
+                pointcloud.run_cloud_outputs(a, pp.mem.device, a.src_hw, stream, img_bgr=img, f_px=a.f_px, z_lo=1e-3,
+                                             z_hi=1e3)
                 if gt_policy:
                     evaluate.driver_score(a, model, gt_policy, gt_maps, pp.mem.device, gt_hw, stream)
                 if a.color:

@@ -32,29 +32,12 @@ at the source size; `--host-postprocess` downloads the 1536^2 map and runs the
 reference's torch-CPU version.  `--f-px` is the reference's f_px0: a known
 focal length in pixels instead of the predicted one.
 
-`--ply PATH` is the reference's `onnx2trt_pointcloud.py:172-184`: the metric
-depth at the source size is unprojected with the focal length (x = (u - W/2) /
-f_px * z, y likewise) and written as a binary PLY, coloured from the `--image`
-photo (no colours with `--input` or the synthetic image).  It runs on the
-device (pointcloud.DevicePointCloud) on the depth map and the focal length the
-device post-process left there, drops depths outside [1e-4, 1e4] and downloads
-the PLY records; `--ply-step N` keeps every N-th pixel on both axes.
-
-`--mesh PATH` is the reference's `models/metric_anything/demo_pointcloud.py:
-142-149`: the samples on a depth edge -- a 3x3 spread of depth above
-`--edge-rtol` (default 0.1, the reference's) times the depth, or above
-`--edge-atol` metres -- are dropped, the 2x2 blocks that survive whole become
-two triangles each, and the vertices they use and the faces are packed on the
-device (pointcloud.DeviceMesh, `mde_op_depth_mesh`) and written as a binary PLY
-with `element vertex` and `element face`.  `--ply-edge-rtol R` gives `--ply`'s
-cloud the same edge filter (no flying pixels), without faces.
-
-`--cloud-view PATH` is the reference's `core/viz.py:render_points` (what
-`demo.py:cloud_figure` shows): an orthographic, z-buffered picture of that
-cloud seen from above-left, drawn on the device from the depth map
-(pointcloud.DeviceCloudView, `mde_op_cloud_view`); only the picture comes
-back.  One `[MDET] cloud view ...` line is printed; the file is written like
-`--color`'s.
+`--ply`, `--mesh` and `--cloud-view` are pointcloud.py's one stage for the
+cloud outputs, described there.  Here they run on the depth map and the focal
+length the device post-process left on the device (`--f-px` instead, when
+given), drop depths outside [1e-4, 1e4] and take their colours from the
+`--image` photo (no colours with `--input` or the synthetic image); none of
+them goes with `--host-postprocess`.
 
 `--gt DEPTH.npy --gt-mask MASK.npy` scores the metric depth against measured
 ground truth of the source size (the reference's tools/evaluate_gt.py:555-583
@@ -82,8 +65,8 @@ import time
 import numpy as np
 
 from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, visualize, weights_depth_pro
-from monocular_depth_estimation_trt_amd.common_runtime import (allocate_buffers, do_inference, free_buffers, hip_call,
-                                                               stream_synchronize)
+from monocular_depth_estimation_trt_amd.common_runtime import (EventPair, allocate_buffers, do_inference,
+                                                               free_buffers, hip_call, stream_synchronize)
 from monocular_depth_estimation_trt_amd import pointcloud
 from monocular_depth_estimation_trt_amd.postprocess import DepthProDevicePostprocess, depth_pro_postprocess
 from monocular_depth_estimation_trt_amd.preprocess import (DepthProPreprocess, load_image_bgr,
@@ -118,11 +101,7 @@ def build_parser(model="depth_pro", size=None):
                     help="focal length in pixels (the reference's f_px0) instead of the predicted one")
     ap.add_argument("--src-hw", type=int, nargs=2, default=None,
                     help="source image size for the post-process (default: the image's / input's own size)")
-    ap.add_argument("--ply", default="", metavar="PATH",
-                    help="write the point cloud (binary PLY; colours from --image) of the metric depth")
-    ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
-    pointcloud.add_mesh_arguments(ap)
-    pointcloud.add_cloud_view_arguments(ap)
+    pointcloud.add_cloud_arguments(ap)
     evaluate.add_gt_arguments(ap)
     visualize.add_color_arguments(ap)
     ap.add_argument("--iterations", type=int, default=100)
@@ -131,86 +110,39 @@ def build_parser(model="depth_pro", size=None):
     return ap
 
 
-class _Events:
-    """A hipEvent pair on one stream; ms() after the stream has synchronized."""
-
-    def __init__(self, stream):
-        self.stream = C.c_void_p(stream)
-        self.ev = [C.c_void_p(), C.c_void_p()]
-        for e in self.ev:
-            hip_call("mde_rt_event_create", C.byref(e))
-
-    def mark(self, i):
-        hip_call("mde_rt_event_record", self.ev[i], self.stream)
-
-    def ms(self):
-        ms = C.c_float()
-        hip_call("mde_rt_event_elapsed_ms", C.byref(ms), self.ev[0], self.ev[1])
-        return float(ms.value)
-
-    def free(self):
-        for e in self.ev:
-            hip_call("mde_rt_event_destroy", e)
-
-
 def _device_preprocess(img, size, mem, stream):
     """DepthProPreprocess into the engine's input binding `mem.device`, timed
     with hipEvents (H2D of the frame + the kernel); the pinned side of the
     binding gets the same bytes back, so the timed loop's upload is a no-op in
     value."""
-    ev = _Events(stream)
-    try:
-        with DepthProPreprocess(img.shape[0], img.shape[1], size) as pre:
-            ev.mark(0)
-            pre.run(img, mem.device, stream)
-            ev.mark(1)
-            hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
-                     mem.nbytes, C.c_void_p(stream))
-            stream_synchronize(stream)
+    with DepthProPreprocess(img.shape[0], img.shape[1], size) as pre, EventPair(stream) as ev:
+        pre.run(img, mem.device, stream)
+        ev.stop()
+        hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
+                 mem.nbytes, C.c_void_p(stream))
+        stream_synchronize(stream)
         return ev.ms()
-    finally:
-        ev.free()
 
 
-def _device_postprocess(outputs, size, src_hw, f_px, stream, ply=None, score=None, color=None, cloud_view=None,
-                        mesh=None):
+def _device_postprocess(outputs, size, src_hw, f_px, stream, consume=None):
     """DepthProDevicePostprocess on the output bindings in place, timed with
-    hipEvents (kernel + D2H of the depth map and the focal length); `ply` =
-    (the parsed arguments, photo or None): then the point cloud of the map,
-    while it is still on the device, with the focal length the post-process
-    used (the fourth result, pointcloud.driver_ply's; else None); `mesh`:
-    called with the map's and the focal length's device pointers (--mesh);
-    `score`: called with
-    the map's device pointer while it is still there (--gt); `color`: likewise
-    (--color); `cloud_view`: likewise, with the device focal length as well
-    (--cloud-view)."""
+    hipEvents (kernel + D2H of the depth map and the focal length).  Returns
+    (depth, f_px, ms); `consume(d_map, d_f_px)` is then called with the device
+    pointers of the map and of the focal length the post-process used, while
+    they are still there -- outside the timed part."""
     if f_px is None and len(outputs) < 2:
         raise SystemExit("this engine has no fov_deg output: pass --f-px")
-    ev = _Events(stream)
-    try:
-        with DepthProDevicePostprocess(1, size, size, *src_hw) as pp:
-            ev.mark(0)
+    with DepthProDevicePostprocess(1, size, size, *src_hw) as pp:
+        with EventPair(stream) as ev:
             pp.enqueue(outputs[0].device, outputs[1].device if len(outputs) > 1 else 0, stream, f_px=f_px)
-            ev.mark(1)
+            ev.stop()
             stream_synchronize(stream)
-            depth, f = pp.result()
-            depth, f, ms = depth[0].copy(), float(f[0]), ev.ms()
-            cloud = None
-            if ply:
-                a, img = ply
-                cloud = pointcloud.driver_ply(a, pp.mem.device, src_hw, stream, img_bgr=img, d_f_px=pp.f_px.device,
-                                              f_px=f_px, z_lo=1e-4, z_hi=1e4)
-            if mesh:
-                mesh(pp.mem.device, pp.f_px.device)
-            if score:
-                score(pp.mem.device)
-            if color:
-                color(pp.mem.device)
-            if cloud_view:
-                cloud_view(pp.mem.device, pp.f_px.device)
-            return depth, f, ms, cloud
-    finally:
-        ev.free()
+            ms = ev.ms()
+        depth, f = pp.result()
+        depth, f = depth[0].copy(), float(f[0])
+        if consume:
+            consume(pp.mem.device, pp.f_px.device)
+        return depth, f, ms
 
 
 def main(argv=None, model="depth_pro"):
@@ -223,19 +155,8 @@ def main(argv=None, model="depth_pro"):
         raise SystemExit("--host-preprocess needs --image")
     if a.f_px is not None and not a.f_px > 0:
         raise SystemExit("--f-px must be positive")
-    if a.ply and a.host_postprocess:
-        raise SystemExit("--ply runs on the device post-process's depth map: do not combine it with "
-                         "--host-postprocess")
-    if a.ply and a.ply_step < 1:
-        raise SystemExit("--ply-step must be positive")
-    if a.mesh and a.host_postprocess:
-        raise SystemExit("--mesh runs on the device post-process's depth map: do not combine it with "
-                         "--host-postprocess")
-    pointcloud.check_mesh_arguments(a)
-    if a.cloud_view and a.host_postprocess:
-        raise SystemExit("--cloud-view runs on the device post-process's depth map: do not combine it with "
-                         "--host-postprocess")
-    pointcloud.check_cloud_view_arguments(a)
+    pointcloud.check_cloud_arguments(
+        a, no_device_map="do not combine it with --host-postprocess" if a.host_postprocess else "")
     gt_policy = evaluate.check_gt_arguments(a, s, device_map=not a.host_postprocess)
     visualize.check_color_arguments(a, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
@@ -256,12 +177,7 @@ def main(argv=None, model="depth_pro"):
         print(f"[MDET] preprocess ({how}) {H}x{W} -> {size}x{size} : {(time.perf_counter() - t0) * 1e3:0.3f} ms")
     src_hw = tuple(a.src_hw) if a.src_hw else (H, W)
     gt_maps = evaluate.load_gt_arguments(a, src_hw) if gt_policy else None
-    if a.ply and img is not None and src_hw != img.shape[:2]:
-        raise SystemExit("--ply takes its colours from the --image photo: --src-hw must be the photo's size")
-    if a.mesh and img is not None and src_hw != img.shape[:2]:
-        raise SystemExit("--mesh takes its colours from the --image photo: --src-hw must be the photo's size")
-    if a.cloud_view and img is not None and src_hw != img.shape[:2]:
-        raise SystemExit("--cloud-view takes its colours from the --image photo: --src-hw must be the photo's size")
+    pointcloud.check_photo_size(a, img, src_hw)
     output_shapes = (1, 1, size, size)
     with common.get_engine(a.source, a.engine, "fp16", None, input_hw=(size, size)) as engine, \
             engine.create_execution_context() as context:
@@ -283,21 +199,17 @@ def main(argv=None, model="depth_pro"):
             print(f"[MDET] postprocess (host, torch) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{(time.perf_counter() - t0) * 1e3:0.3f} ms")
         else:  # the engine's outputs are still in outputs[*].device
-            score = (lambda d_map: evaluate.driver_score(a, model, gt_policy, gt_maps, d_map, src_hw, stream)) if gt_policy \
-                else None
-            color = (lambda d_map: visualize.driver_color(a, s, d_map, src_hw, stream)) if a.color else None
-            view = (lambda d_map, d_f: pointcloud.driver_cloud_view(a, d_map, src_hw, stream, img_bgr=img, d_f_px=d_f,
-                                                                    f_px=a.f_px)) if a.cloud_view else None
-            mesh = (lambda d_map, d_f: pointcloud.driver_mesh(a, d_map, src_hw, stream, img_bgr=img, d_f_px=d_f,
-                                                              f_px=a.f_px, z_lo=1e-4, z_hi=1e4)) if a.mesh else None
-            depth, f_px, ms, cloud = _device_postprocess(outputs, size, src_hw, a.f_px, stream,
-                                                         ply=(a, img) if a.ply else None, score=score,
-                                                         color=color, cloud_view=view, mesh=mesh)
+            def consume(d_map, d_f_px):
+                pointcloud.run_cloud_outputs(a, d_map, src_hw, stream, img_bgr=img, d_f_px=d_f_px, f_px=a.f_px,
+                                             z_lo=1e-4, z_hi=1e4)
+                if gt_policy:
+                    evaluate.driver_score(a, model, gt_policy, gt_maps, d_map, src_hw, stream)
+                if a.color:
+                    visualize.driver_color(a, s, d_map, src_hw, stream)
+
+            depth, f_px, ms = _device_postprocess(outputs, size, src_hw, a.f_px, stream, consume)
             print(f"[MDET] postprocess (device, kernel + D2H, hipEvents) {size}x{size} -> {src_hw[0]}x{src_hw[1]} : "
                   f"{ms:0.3f} ms")
-            if cloud:
-                print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {src_hw[0]}x{src_hw[1]} step "
-                      f"{a.ply_step} -> {a.ply} : {cloud[0]:0.3f} ms, {cloud[1]} points")
         bench.record(model, samples, encoder="fixed", warmup=a.warmup, precision="fp16", profile="native",
                      input_h=size, input_w=size, engine_path=a.engine, outputs={"depth": depth, "f_px": np.array(f_px)},
                      notes=f"source={a.source}; 1536x1536 is upstream fixed", model_input=x, out_dir=a.out_dir)

@@ -64,10 +64,7 @@ def build_parser(model="depth_pro", size=None):
                     help="focal length in pixels instead of the predicted one")
     ap.add_argument("--cloud-view-out", default="", metavar="VIEWS.npy",
                     help="where the uint8 [T,h,w,3] BGR point-cloud previews go (camera fixed from the first frame)")
-    ap.add_argument("--cloud-view-size", type=int, nargs=2, default=list(pointcloud.VIEW_SIZE), metavar=("H", "W"))
-    ap.add_argument("--cloud-view-angles", type=float, nargs=2, default=list(pointcloud.VIEW_ANGLES),
-                    metavar=("ELEV", "AZIM"))
-    ap.add_argument("--cloud-view-step", type=int, default=1, help="draw every N-th pixel on both axes")
+    pointcloud.add_cloud_view_arguments(ap, picture=False)
     return ap
 
 

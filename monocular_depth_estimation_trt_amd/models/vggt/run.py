@@ -46,7 +46,7 @@ import time
 import numpy as np
 
 from monocular_depth_estimation_trt_amd import bench, common, spec, visualize, weights_vggt
-from monocular_depth_estimation_trt_amd.common_runtime import (HostDeviceMem, allocate_buffers, do_inference,
+from monocular_depth_estimation_trt_amd.common_runtime import (EventPair, HostDeviceMem, allocate_buffers, do_inference,
                                                                free_buffers, hip_call, stream_synchronize)
 from monocular_depth_estimation_trt_amd.preprocess import (VggtPreprocess, box_window, crop_f32, load_image_bgr,
                                                            preprocess_vggt_host)
@@ -101,24 +101,14 @@ def _device_preprocess(frames, size, mem, stream):
     with hipEvents (H2D of the frames + the kernel); the pinned side of the
     binding gets the same bytes back, so the timed loop's upload is a no-op in
     value.  Returns (ms, box)."""
-    ev = [C.c_void_p(), C.c_void_p()]
-    for e in ev:
-        hip_call("mde_rt_event_create", C.byref(e))
-    try:
-        with VggtPreprocess(frames.shape[1], frames.shape[2], size, frames=frames.shape[0]) as pre:
-            hip_call("mde_rt_event_record", ev[0], C.c_void_p(stream))
-            pre.run(frames, mem.device, stream)
-            hip_call("mde_rt_event_record", ev[1], C.c_void_p(stream))
-            hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
-                     mem.nbytes, C.c_void_p(stream))
-            stream_synchronize(stream)
-            box = pre.box
-        ms = C.c_float()
-        hip_call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
-    finally:
-        for e in ev:
-            hip_call("mde_rt_event_destroy", e)
-    return float(ms.value), box
+    with VggtPreprocess(frames.shape[1], frames.shape[2], size, frames=frames.shape[0]) as pre, \
+            EventPair(stream) as ev:
+        pre.run(frames, mem.device, stream)
+        ev.stop()
+        hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
+                 mem.nbytes, C.c_void_p(stream))
+        stream_synchronize(stream)
+        return ev.ms(), pre.box
 
 
 def _frame_path(path: str, i: int) -> str:

@@ -26,17 +26,51 @@ per surviving 2 x 2 block, no unreferenced vertices -- is `mde_op_depth_mesh`
 kernels are held to it byte for byte), `DeviceMesh` owns the buffers and
 drives the op, `write_ply_mesh` / `read_ply_mesh` handle the vertex + face
 PLY, `device_mesh` is what the drivers' `--mesh` and `--ply-edge-rtol` call.
+
+The three Device* classes take the same cloud source -- a device depth map, a
+sampling step, an optional device photo, a focal length on the device or on
+the host, cx, cy -- and share `_CloudOp` for it.
+
+The drivers' cloud outputs (models/depth_pro/run.py, models/depth_anything_v2/
+run.py and the models that go through it) are one stage here:
+`add_cloud_arguments` declares the options, `check_cloud_arguments` and
+`check_photo_size` refuse what cannot be served, `run_cloud_outputs` uploads
+the `--image` photo once and runs, in this order, each with one `[MDET]` line:
+
+`--ply PATH [--ply-step N]`: the reference's onnx2trt_pointcloud.py:172-184.
+The metric depth at the source size is unprojected with the focal length
+(x = (u - W/2) / f_px * z, y likewise) and written as a binary PLY, coloured
+from the `--image` photo (no colours without one).  It runs on the device
+(`DevicePointCloud`) on the map the device post-process left there, drops
+depths outside the driver's clamp and downloads the PLY records; `--ply-step
+N` keeps every N-th pixel on both axes.  `--ply-edge-rtol R` gives the cloud
+`--mesh`'s edge filter (no flying pixels), without faces.
+
+`--mesh PATH [--mesh-step N] [--edge-rtol R] [--edge-atol A]`: the reference's
+demo_pointcloud.py:142-149.  The samples on a depth edge -- a 3x3 spread of
+depth above `--edge-rtol` (default 0.1, the reference's) times the depth, or
+above `--edge-atol` metres -- are dropped, the 2x2 blocks that survive whole
+become two triangles each, and the vertices they use and the faces are packed
+on the device (`DeviceMesh`) and written as a binary PLY with `element vertex`
+and `element face`.
+
+`--cloud-view PATH [--cloud-view-size H W] [--cloud-view-angles ELEV AZIM]
+[--cloud-view-step N]`: the reference's core/viz.py:render_points.  An
+orthographic, z-buffered picture of that cloud seen from above-left, drawn on
+the device (`DeviceCloudView`); only the picture comes back, and the file is
+written like `--color`'s (visualize.save_image).
 """
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import List, Optional
 
 import numpy as np
 
 from . import _lib
-from .common_runtime import HostDeviceMem, stream_synchronize
+from .common_runtime import EventPair, HostDeviceMem, stream_synchronize
 
 _XYZ = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
 _RGB = [("red", "u1"), ("green", "u1"), ("blue", "u1")]
@@ -116,7 +150,82 @@ def point_cloud(d_depth: int, batch: int, h: int, w: int, step: int, d_photo: in
               int(ws_nbytes), C.c_void_p(int(stream or 0)))
 
 
-class DevicePointCloud:
+class _CloudOp:
+    """What DevicePointCloud, DeviceMesh and DeviceCloudView share: the cloud
+    source's geometry and `colour` flag, the op's scratch, the checks and the
+    camera defaults of enqueue's source arguments, and the release.  A
+    subclass names its op and its HostDeviceMem attributes; the first of them
+    being None means freed."""
+
+    _OP = ""
+    _BUFFERS = ()
+
+    def __init__(self, batch: int, h: int, w: int, colour: bool, step: int):
+        self.batch, self.h, self.w, self.step = int(batch), int(h), int(w), int(step)
+        self.colour = bool(colour)
+        for name in self._BUFFERS:
+            setattr(self, name, None)
+        self._ws = 0
+        self._ws_bytes = 0
+
+    def _allocate(self, ws_nbytes: int, geometry: str, **buffers) -> None:
+        """The scratch of `ws_nbytes` (0: the op refuses `geometry`) and the
+        named buffers, each a (size, dtype) for HostDeviceMem."""
+        self._ws_bytes = ws_nbytes
+        if ws_nbytes == 0:
+            raise ValueError(f"{self._OP} does not take {geometry}")
+        try:
+            for name, (size, dtype) in buffers.items():
+                setattr(self, name, HostDeviceMem(size, dtype))
+            p = C.c_void_p()
+            _lib.call("mde_rt_malloc", C.byref(p), self._ws_bytes)
+            self._ws = int(p.value)
+        except Exception:
+            self.free()
+            raise
+
+    def _live(self) -> None:
+        if getattr(self, self._BUFFERS[0]) is None:
+            raise RuntimeError(f"{type(self).__name__} already freed")
+
+    def _source(self, d_depth, d_photo, pitch, swap_rb, d_f_px, fx, fy, cx, cy):
+        """The thirteen cloud-source arguments of the op from enqueue's: fy
+        defaults to fx, cx, cy to w / 2, h / 2 like the reference, the pitch to
+        packed rows."""
+        name = type(self).__name__
+        self._live()
+        if bool(d_photo) != self.colour:
+            raise ValueError(f"{name}(colour={self.colour}) {'needs' if self.colour else 'does not take'} a photo")
+        if not d_f_px and fx is None:
+            raise ValueError(f"{name}.enqueue needs d_f_px or fx")
+        fx = 0.0 if fx is None else float(fx)
+        fy = fx if fy is None else float(fy)
+        return (d_depth, self.batch, self.h, self.w, self.step, d_photo, pitch or 3 * self.w, swap_rb, d_f_px, fx, fy,
+                self.w / 2 if cx is None else cx, self.h / 2 if cy is None else cy)
+
+    def run(self, d_depth: int, stream: int, **kw):
+        self.enqueue(d_depth, stream, **kw)
+        self.download(stream)
+        return self.result()
+
+    def free(self) -> None:
+        for name in self._BUFFERS:
+            if getattr(self, name) is not None:
+                getattr(self, name).free()
+            setattr(self, name, None)
+        if self._ws:
+            _lib.call("mde_rt_free", C.c_void_p(self._ws))
+            self._ws = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+
+class DevicePointCloud(_CloudOp):
     """Owns the vertex records and the counts (device + pinned host) and the
     compaction scratch for `batch` depth maps [h, w], with or without colour,
     sampling every `step`-th pixel.
@@ -127,27 +236,16 @@ class DevicePointCloud:
     is one `vertex_dtype` view of counts[b] records per image, valid until the
     next download; run() = enqueue, download, result."""
 
+    _OP = "mde_op_point_cloud"
+    _BUFFERS = ("records", "counts")
+
     def __init__(self, batch: int, h: int, w: int, colour: bool, step: int = 1):
-        self.batch, self.h, self.w, self.step = int(batch), int(h), int(w), int(step)
-        self.colour = bool(colour)
+        super().__init__(batch, h, w, colour, step)
         self.hs, self.ws = grid(self.h, self.w, self.step)
         self.dtype = vertex_dtype(self.colour)
         self.region = self.hs * self.ws * self.dtype.itemsize  # bytes per image
-        self.records: Optional[HostDeviceMem] = None
-        self.counts: Optional[HostDeviceMem] = None
-        self._ws = 0
-        self._ws_bytes = ws_bytes(self.batch, self.h, self.w, self.step)
-        if self._ws_bytes == 0:
-            raise ValueError(f"mde_op_point_cloud does not take batch {batch}, {h}x{w}, step {step}")
-        try:
-            self.records = HostDeviceMem(self.batch * self.region, np.uint8)
-            self.counts = HostDeviceMem(self.batch, np.dtype(np.int32))
-            p = C.c_void_p()
-            _lib.call("mde_rt_malloc", C.byref(p), self._ws_bytes)
-            self._ws = int(p.value)
-        except Exception:
-            self.free()
-            raise
+        self._allocate(ws_bytes(self.batch, self.h, self.w, self.step), f"batch {batch}, {h}x{w}, step {step}",
+                       records=(self.batch * self.region, np.uint8), counts=(self.batch, np.dtype(np.int32)))
 
     def enqueue(self, d_depth: int, stream: int, d_photo: int = 0, pitch: int = 0, swap_rb: bool = False,
                 d_f_px: int = 0, fx: Optional[float] = None, fy: Optional[float] = None,
@@ -156,23 +254,12 @@ class DevicePointCloud:
         """The kernels on `stream`, nothing else.  d_f_px: device float[batch]
         focal lengths (DepthProDevicePostprocess.f_px.device), else fx (and fy,
         default fx); cx, cy default to w / 2, h / 2 like the reference."""
-        if self.records is None:
-            raise RuntimeError("DevicePointCloud already freed")
-        if bool(d_photo) != self.colour:
-            raise ValueError("DevicePointCloud(colour=%s) %s a photo" % (self.colour, "needs" if self.colour else
-                                                                         "does not take"))
-        if not d_f_px and fx is None:
-            raise ValueError("DevicePointCloud.enqueue needs d_f_px or fx")
-        fx = 0.0 if fx is None else float(fx)
-        fy = fx if fy is None else float(fy)
-        point_cloud(d_depth, self.batch, self.h, self.w, self.step, d_photo, pitch or 3 * self.w, swap_rb, d_f_px,
-                    fx, fy, self.w / 2 if cx is None else cx, self.h / 2 if cy is None else cy, compact, z_lo, z_hi,
+        point_cloud(*self._source(d_depth, d_photo, pitch, swap_rb, d_f_px, fx, fy, cx, cy), compact, z_lo, z_hi,
                     self.records.device, self.records.nbytes, self.counts.device, self._ws, self._ws_bytes, stream)
 
     def download(self, stream: int) -> None:
         """Counts first, then only the counted bytes; synchronizes `stream` twice."""
-        if self.records is None:
-            raise RuntimeError("DevicePointCloud already freed")
+        self._live()
         s = C.c_void_p(int(stream or 0))
         _lib.call("mde_rt_memcpy_dtoh_async", self.counts.host.ctypes.data_as(C.c_void_p),
                   C.c_void_p(self.counts.device), self.counts.nbytes, s)
@@ -187,73 +274,59 @@ class DevicePointCloud:
 
     def result(self) -> List[np.ndarray]:
         """One view of counts[b] records per image; valid after download()."""
-        if self.records is None:
-            raise RuntimeError("DevicePointCloud already freed")
+        self._live()
         host, item = self.records.host, self.dtype.itemsize
         return [host[b * self.region:b * self.region + int(self.counts.host[b]) * item].view(self.dtype)
                 for b in range(self.batch)]
 
-    def run(self, d_depth: int, stream: int, **kw) -> List[np.ndarray]:
-        self.enqueue(d_depth, stream, **kw)
-        self.download(stream)
-        return self.result()
 
-    def free(self) -> None:
-        for m in (self.records, self.counts):
-            if m is not None:
-                m.free()
-        self.records = self.counts = None
-        if self._ws:
-            _lib.call("mde_rt_free", C.c_void_p(self._ws))
-            self._ws = 0
+@contextlib.contextmanager
+def _device_photo(img_bgr, d_photo: int, h: int, w: int, stream: int):
+    """The device pointer of the drivers' BGR photo (0: no colours): `d_photo`
+    when the caller has uploaded it already, else `img_bgr`, checked against
+    uint8 [h, w, 3] and uploaded once on `stream`, freed when the block ends."""
+    if d_photo or img_bgr is None:
+        yield int(d_photo or 0)
+        return
+    if img_bgr.dtype != np.uint8 or img_bgr.shape != (h, w, 3):
+        raise ValueError(f"the photo must be uint8 [{h}, {w}, 3], got {img_bgr.dtype} {img_bgr.shape}")
+    photo = HostDeviceMem(h * w * 3, np.uint8)
+    try:
+        photo.host = np.ascontiguousarray(img_bgr).reshape(-1)
+        _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(photo.device), photo.host.ctypes.data_as(C.c_void_p),
+                  photo.nbytes, C.c_void_p(int(stream or 0)))
+        yield photo.device
+    finally:
+        photo.free()
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.free()
-        return False
+def _timed(op: _CloudOp, d_depth: int, stream: int, d_photo: int, d_f_px: int, f_px, **kw) -> float:
+    """enqueue + download of `op` with the drivers' camera -- the BGR photo at
+    `d_photo`, the given `f_px` or else the device focal length `d_f_px`, cx,
+    cy = w / 2, h / 2 -- between two hipEvents on `stream`; the ms."""
+    with EventPair(stream) as ev:
+        op.enqueue(d_depth, stream, d_photo=d_photo, pitch=3 * op.w, swap_rb=True,
+                   d_f_px=0 if f_px is not None else d_f_px, fx=f_px, **kw)
+        op.download(stream)
+        ev.stop()
+        stream_synchronize(stream)
+        return ev.ms()
 
 
 def device_ply(path, d_depth: int, h: int, w: int, stream: int, step: int = 1, img_bgr: Optional[np.ndarray] = None,
-               d_f_px: int = 0, f_px: Optional[float] = None, z_lo: float = 1e-4, z_hi: float = 1e4):
+               d_f_px: int = 0, f_px: Optional[float] = None, z_lo: float = 1e-4, z_hi: float = 1e4, d_photo: int = 0):
     """What the model drivers' --ply does: DevicePointCloud in compact mode on
     one device depth map [h][w] at `d_depth`, with the given `f_px` or else the
     device focal length `d_f_px`, cx, cy = w / 2, h / 2, colours from the BGR
-    photo `img_bgr` [h, w, 3] (uploaded here, once, before the timed part),
-    written to `path`.  Returns (ms of the kernels + D2H between two hipEvents
-    on `stream`, number of points)."""
-    if img_bgr is not None and (img_bgr.dtype != np.uint8 or img_bgr.shape != (h, w, 3)):
-        raise ValueError(f"the photo must be uint8 [{h}, {w}, 3], got {img_bgr.dtype} {img_bgr.shape}")
-    s = C.c_void_p(int(stream or 0))
-    photo = None
-    ev = [C.c_void_p(), C.c_void_p()]
-    try:
-        for e in ev:
-            _lib.call("mde_rt_event_create", C.byref(e))
-        if img_bgr is not None:
-            photo = HostDeviceMem(h * w * 3, np.uint8)
-            photo.host = np.ascontiguousarray(img_bgr).reshape(-1)
-            _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(photo.device), photo.host.ctypes.data_as(C.c_void_p),
-                      photo.nbytes, s)
-        with DevicePointCloud(1, h, w, colour=photo is not None, step=step) as cloud:
-            _lib.call("mde_rt_event_record", ev[0], s)
-            cloud.enqueue(d_depth, stream, d_photo=photo.device if photo else 0, pitch=3 * w, swap_rb=True,
-                          d_f_px=0 if f_px is not None else d_f_px, fx=f_px, z_lo=z_lo, z_hi=z_hi)
-            cloud.download(stream)
-            _lib.call("mde_rt_event_record", ev[1], s)
-            stream_synchronize(stream)
-            records = cloud.result()[0]
-            write_ply(path, records)
-            ms = C.c_float()
-            _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
-            return float(ms.value), int(records.shape[0])
-    finally:
-        if photo is not None:
-            photo.free()
-        for e in ev:
-            if e:
-                _lib.call("mde_rt_event_destroy", e)
+    photo `img_bgr` [h, w, 3] (uploaded here, once, before the timed part) or
+    the one already at `d_photo`, written to `path`.  Returns (ms of the
+    kernels + D2H between two hipEvents on `stream`, number of points)."""
+    with _device_photo(img_bgr, d_photo, h, w, stream) as d_photo, \
+            DevicePointCloud(1, h, w, colour=bool(d_photo), step=step) as cloud:
+        ms = _timed(cloud, d_depth, stream, d_photo, d_f_px, f_px, z_lo=z_lo, z_hi=z_hi)
+        records = cloud.result()[0]
+        write_ply(path, records)
+        return ms, int(records.shape[0])
 
 
 VIEW_ROW = 8             # doubles per view row of mde_op_cloud_view
@@ -367,7 +440,7 @@ def cloud_view(d_depth: int, batch: int, h: int, w: int, step: int, d_photo: int
               C.c_void_p(int(stream or 0)))
 
 
-class DeviceCloudView:
+class DeviceCloudView(_CloudOp):
     """Owns the pictures uint8 [batch][out_h][out_w][3] and the view rows
     float64 [batch][8] (device + pinned host) and the scratch of
     mde_op_cloud_view for `batch` depth maps [h, w], with or without colour,
@@ -380,28 +453,16 @@ class DeviceCloudView:
     the [batch, 8] rows, valid until the next download; run() = enqueue,
     download, result."""
 
+    _OP = "mde_op_cloud_view"
+    _BUFFERS = ("pictures", "views", "view_in")
+
     def __init__(self, batch: int, h: int, w: int, out_hw=VIEW_SIZE, colour: bool = True, step: int = 1):
-        self.batch, self.h, self.w, self.step = int(batch), int(h), int(w), int(step)
+        super().__init__(batch, h, w, colour, step)
         self.out_h, self.out_w = int(out_hw[0]), int(out_hw[1])
-        self.colour = bool(colour)
-        self.pictures: Optional[HostDeviceMem] = None
-        self.views: Optional[HostDeviceMem] = None
-        self.view_in: Optional[HostDeviceMem] = None
-        self._ws = 0
-        self._ws_bytes = cloud_view_ws_bytes(self.batch, self.h, self.w, self.step, self.out_h, self.out_w)
-        if self._ws_bytes == 0:
-            raise ValueError(f"mde_op_cloud_view does not take batch {batch}, {h}x{w}, step {step}, picture "
-                             f"{self.out_h}x{self.out_w}")
-        try:
-            self.pictures = HostDeviceMem(self.batch * self.out_h * self.out_w * 3, np.uint8)
-            self.views = HostDeviceMem(self.batch * VIEW_ROW, np.dtype(np.float64))
-            self.view_in = HostDeviceMem(self.batch * VIEW_ROW, np.dtype(np.float64))
-            p = C.c_void_p()
-            _lib.call("mde_rt_malloc", C.byref(p), self._ws_bytes)
-            self._ws = int(p.value)
-        except Exception:
-            self.free()
-            raise
+        rows = (self.batch * VIEW_ROW, np.dtype(np.float64))
+        self._allocate(cloud_view_ws_bytes(self.batch, self.h, self.w, self.step, self.out_h, self.out_w),
+                       f"batch {batch}, {h}x{w}, step {step}, picture {self.out_h}x{self.out_w}",
+                       pictures=(self.batch * self.out_h * self.out_w * 3, np.uint8), views=rows, view_in=rows)
 
     def enqueue(self, d_depth: int, stream: int, d_photo: int = 0, pitch: int = 0, swap_rb: bool = False,
                 d_f_px: int = 0, fx: Optional[float] = None, fy: Optional[float] = None,
@@ -413,33 +474,22 @@ class DeviceCloudView:
         row for all) whose centre and scale fix the camera; `d_view`: the same
         already in device memory -- `self.views.device` keeps the camera of
         the previous enqueue."""
-        if self.pictures is None:
-            raise RuntimeError("DeviceCloudView already freed")
-        if bool(d_photo) != self.colour:
-            raise ValueError("DeviceCloudView(colour=%s) %s a photo" % (self.colour, "needs" if self.colour else
-                                                                        "does not take"))
-        if not d_f_px and fx is None:
-            raise ValueError("DeviceCloudView.enqueue needs d_f_px or fx")
+        source = self._source(d_depth, d_photo, pitch, swap_rb, d_f_px, fx, fy, cx, cy)
         if view is not None and d_view:
             raise ValueError("DeviceCloudView.enqueue takes view or d_view, not both")
-        fx = 0.0 if fx is None else float(fx)
-        fy = fx if fy is None else float(fy)
         if view is not None:
             rows = np.broadcast_to(np.asarray(view, dtype=np.float64).reshape(-1, VIEW_ROW), (self.batch, VIEW_ROW))
             self.view_in.host = np.ascontiguousarray(rows).reshape(-1)
             _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(self.view_in.device),
                       self.view_in.host.ctypes.data_as(C.c_void_p), self.view_in.nbytes, C.c_void_p(int(stream or 0)))
             d_view = self.view_in.device
-        cloud_view(d_depth, self.batch, self.h, self.w, self.step, d_photo, pitch or 3 * self.w, swap_rb, d_f_px, fx,
-                   fy, self.w / 2 if cx is None else cx, self.h / 2 if cy is None else cy,
-                   view_trig(elev_deg, azim_deg), d_view, bg, out_swap_rb, self.pictures.device, self.out_h,
+        cloud_view(*source, view_trig(elev_deg, azim_deg), d_view, bg, out_swap_rb, self.pictures.device, self.out_h,
                    self.out_w, self.views.device, self._ws, self._ws_bytes, stream)
 
     def download(self, stream: int, sync: bool = True) -> None:
         """The pictures and the view rows; synchronizes `stream` unless `sync`
         is off (the caller's own synchronisation then makes them valid)."""
-        if self.pictures is None:
-            raise RuntimeError("DeviceCloudView already freed")
+        self._live()
         s = C.c_void_p(int(stream or 0))
         for m in (self.pictures, self.views):
             _lib.call("mde_rt_memcpy_dtoh_async", m.host.ctypes.data_as(C.c_void_p), C.c_void_p(m.device), m.nbytes, s)
@@ -448,85 +498,37 @@ class DeviceCloudView:
 
     def result(self) -> np.ndarray:
         """uint8 [batch, out_h, out_w, 3]; valid after download()."""
-        if self.pictures is None:
-            raise RuntimeError("DeviceCloudView already freed")
+        self._live()
         return self.pictures.host.reshape(self.batch, self.out_h, self.out_w, 3)
 
     def view(self) -> np.ndarray:
         """float64 [batch, 8] view rows; valid after download()."""
-        if self.views is None:
-            raise RuntimeError("DeviceCloudView already freed")
+        self._live()
         return self.views.host.reshape(self.batch, VIEW_ROW)
-
-    def run(self, d_depth: int, stream: int, **kw) -> np.ndarray:
-        self.enqueue(d_depth, stream, **kw)
-        self.download(stream)
-        return self.result()
-
-    def free(self) -> None:
-        for m in (self.pictures, self.views, self.view_in):
-            if m is not None:
-                m.free()
-        self.pictures = self.views = self.view_in = None
-        if self._ws:
-            _lib.call("mde_rt_free", C.c_void_p(self._ws))
-            self._ws = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
 
 
 def device_cloud_view(path, d_depth: int, h: int, w: int, stream: int, size=VIEW_SIZE, elev_deg: float = VIEW_ANGLES[0],
                       azim_deg: float = VIEW_ANGLES[1], step: int = 1, img_bgr: Optional[np.ndarray] = None,
-                      d_f_px: int = 0, f_px: Optional[float] = None):
+                      d_f_px: int = 0, f_px: Optional[float] = None, d_photo: int = 0):
     """What the model drivers' --cloud-view does: DeviceCloudView on one device
-    depth map [h][w] at `d_depth`, with the given `f_px` or else the device
-    focal length `d_f_px`, cx, cy = w / 2, h / 2, colours from the BGR photo
-    `img_bgr` [h, w, 3] (uploaded here, once, before the timed part); the BGR
-    picture goes to `path` through visualize.save_image.  Returns (ms of the
-    kernels + D2H between two hipEvents on `stream`, the view row)."""
+    depth map [h][w] at `d_depth`, camera and colours as for `device_ply`; the
+    BGR picture goes to `path` through visualize.save_image.  Returns (ms of
+    the kernels + D2H between two hipEvents on `stream`, the view row)."""
     from .visualize import save_image
-    if img_bgr is not None and (img_bgr.dtype != np.uint8 or img_bgr.shape != (h, w, 3)):
-        raise ValueError(f"the photo must be uint8 [{h}, {w}, 3], got {img_bgr.dtype} {img_bgr.shape}")
-    s = C.c_void_p(int(stream or 0))
-    photo = None
-    ev = [C.c_void_p(), C.c_void_p()]
-    try:
-        for e in ev:
-            _lib.call("mde_rt_event_create", C.byref(e))
-        if img_bgr is not None:
-            photo = HostDeviceMem(h * w * 3, np.uint8)
-            photo.host = np.ascontiguousarray(img_bgr).reshape(-1)
-            _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(photo.device), photo.host.ctypes.data_as(C.c_void_p),
-                      photo.nbytes, s)
-        with DeviceCloudView(1, h, w, size, colour=photo is not None, step=step) as cv:
-            _lib.call("mde_rt_event_record", ev[0], s)
-            cv.enqueue(d_depth, stream, d_photo=photo.device if photo else 0, pitch=3 * w, swap_rb=True,
-                       d_f_px=0 if f_px is not None else d_f_px, fx=f_px, elev_deg=elev_deg, azim_deg=azim_deg,
-                       out_swap_rb=True)
-            cv.download(stream)
-            _lib.call("mde_rt_event_record", ev[1], s)
-            stream_synchronize(stream)
-            save_image(str(path), cv.result()[0])
-            ms = C.c_float()
-            _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
-            return float(ms.value), cv.view()[0].copy()
-    finally:
-        if photo is not None:
-            photo.free()
-        for e in ev:
-            if e:
-                _lib.call("mde_rt_event_destroy", e)
+    with _device_photo(img_bgr, d_photo, h, w, stream) as d_photo, \
+            DeviceCloudView(1, h, w, size, colour=bool(d_photo), step=step) as cv:
+        ms = _timed(cv, d_depth, stream, d_photo, d_f_px, f_px, elev_deg=elev_deg, azim_deg=azim_deg,
+                    out_swap_rb=True)
+        save_image(str(path), cv.result()[0])
+        return ms, cv.view()[0].copy()
 
 
-def add_cloud_view_arguments(ap) -> None:
-    """The drivers' --cloud-view options."""
-    ap.add_argument("--cloud-view", default="", metavar="PATH",
-                    help="write a z-buffered orthographic picture of the point cloud (colours from --image)")
+def add_cloud_view_arguments(ap, picture: bool = True) -> None:
+    """The drivers' --cloud-view options; `picture` off: only its size, angles
+    and step (models/depth_pro/stream.py names its own output)."""
+    if picture:
+        ap.add_argument("--cloud-view", default="", metavar="PATH",
+                        help="write a z-buffered orthographic picture of the point cloud (colours from --image)")
     ap.add_argument("--cloud-view-size", type=int, nargs=2, default=list(VIEW_SIZE), metavar=("H", "W"))
     ap.add_argument("--cloud-view-angles", type=float, nargs=2, default=list(VIEW_ANGLES), metavar=("ELEV", "AZIM"),
                     help="degrees; the default looks from above-left")
@@ -545,12 +547,12 @@ def check_cloud_view_arguments(a) -> None:
         raise SystemExit("--cloud-view-angles must be finite")
 
 
-def driver_cloud_view(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None):
+def driver_cloud_view(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, d_photo: int = 0):
     """The drivers' --cloud-view: the picture of the device map [hw] at
     `d_depth` and its `[MDET] cloud view ...` line.  Returns the view row."""
     ms, row = device_cloud_view(a.cloud_view, d_depth, hw[0], hw[1], stream, size=a.cloud_view_size,
                                 elev_deg=a.cloud_view_angles[0], azim_deg=a.cloud_view_angles[1],
-                                step=a.cloud_view_step, img_bgr=img_bgr, d_f_px=d_f_px, f_px=f_px)
+                                step=a.cloud_view_step, img_bgr=img_bgr, d_f_px=d_f_px, f_px=f_px, d_photo=d_photo)
     print(f"[MDET] cloud view (device, kernels + D2H, hipEvents) {hw[0]}x{hw[1]} step {a.cloud_view_step} -> "
           f"{a.cloud_view_size[0]}x{a.cloud_view_size[1]} {a.cloud_view} : {ms:0.3f} ms, {int(row[V_NVALID])} valid "
           f"points, {int(row[V_INSIDE])} inside the picture")
@@ -698,7 +700,7 @@ def depth_mesh(d_depth: int, batch: int, h: int, w: int, step: int, d_photo: int
               C.c_void_p(int(stream or 0)))
 
 
-class DeviceMesh:
+class DeviceMesh(_CloudOp):
     """Owns the vertex and face records and the two counts (device + pinned
     host) and the scratch of mde_op_depth_mesh for `batch` depth maps [h, w],
     with or without colour, sampling every `step`-th pixel; `faces` off: the
@@ -710,31 +712,21 @@ class DeviceMesh:
     result() is one (`vertex_dtype` view, FACE_DTYPE view) pair per image,
     valid until the next download; run() = enqueue, download, result."""
 
+    _OP = "mde_op_depth_mesh"
+    _BUFFERS = ("vertices", "face_records", "counts")  # counts [2][batch]: vertices, triangles
+
     def __init__(self, batch: int, h: int, w: int, colour: bool, step: int = 1, faces: bool = True):
-        self.batch, self.h, self.w, self.step = int(batch), int(h), int(w), int(step)
-        self.colour, self.faces = bool(colour), bool(faces)
+        super().__init__(batch, h, w, colour, step)
+        self.faces = bool(faces)
         self.hs, self.ws = grid(self.h, self.w, self.step)
         self.dtype = vertex_dtype(self.colour)
         self.region = self.hs * self.ws * self.dtype.itemsize                       # vertex bytes per image
         self.face_region = 2 * (self.hs - 1) * (self.ws - 1) * FACE_DTYPE.itemsize  # face bytes per image
-        self.vertices: Optional[HostDeviceMem] = None
-        self.face_records: Optional[HostDeviceMem] = None
-        self.counts: Optional[HostDeviceMem] = None  # [2][batch]: vertices, triangles
-        self._ws = 0
-        self._ws_bytes = mesh_ws_bytes(self.batch, self.h, self.w, self.step)
-        if self._ws_bytes == 0:
-            raise ValueError(f"mde_op_depth_mesh does not take batch {batch}, {h}x{w}, step {step}")
-        try:
-            self.vertices = HostDeviceMem(self.batch * self.region, np.uint8)
-            if self.faces:  # at least one byte: the op wants a pointer even where no quad exists
-                self.face_records = HostDeviceMem(max(self.batch * self.face_region, 1), np.uint8)
-            self.counts = HostDeviceMem(2 * self.batch, np.dtype(np.int32))
-            p = C.c_void_p()
-            _lib.call("mde_rt_malloc", C.byref(p), self._ws_bytes)
-            self._ws = int(p.value)
-        except Exception:
-            self.free()
-            raise
+        buffers = dict(vertices=(self.batch * self.region, np.uint8))
+        if self.faces:  # at least one byte: the op wants a pointer even where no quad exists
+            buffers["face_records"] = (max(self.batch * self.face_region, 1), np.uint8)
+        self._allocate(mesh_ws_bytes(self.batch, self.h, self.w, self.step), f"batch {batch}, {h}x{w}, step {step}",
+                       **buffers, counts=(2 * self.batch, np.dtype(np.int32)))
 
     def enqueue(self, d_depth: int, stream: int, d_photo: int = 0, pitch: int = 0, swap_rb: bool = False,
                 d_f_px: int = 0, fx: Optional[float] = None, fy: Optional[float] = None,
@@ -742,25 +734,14 @@ class DeviceMesh:
                 edge_rtol: float = EDGE_RTOL, edge_atol: float = 0.0) -> None:
         """The kernels on `stream`, nothing else.  Focal lengths and cx, cy as
         for DevicePointCloud.enqueue."""
-        if self.vertices is None:
-            raise RuntimeError("DeviceMesh already freed")
-        if bool(d_photo) != self.colour:
-            raise ValueError("DeviceMesh(colour=%s) %s a photo" % (self.colour, "needs" if self.colour else
-                                                                   "does not take"))
-        if not d_f_px and fx is None:
-            raise ValueError("DeviceMesh.enqueue needs d_f_px or fx")
-        fx = 0.0 if fx is None else float(fx)
-        fy = fx if fy is None else float(fy)
-        depth_mesh(d_depth, self.batch, self.h, self.w, self.step, d_photo, pitch or 3 * self.w, swap_rb, d_f_px, fx,
-                   fy, self.w / 2 if cx is None else cx, self.h / 2 if cy is None else cy, z_lo, z_hi, edge_rtol,
+        depth_mesh(*self._source(d_depth, d_photo, pitch, swap_rb, d_f_px, fx, fy, cx, cy), z_lo, z_hi, edge_rtol,
                    edge_atol, self.faces, self.vertices.device, self.batch * self.region, self.counts.device,
                    self.face_records.device if self.faces else 0, self.batch * self.face_region if self.faces else 0,
                    self.counts.device + 4 * self.batch if self.faces else 0, self._ws, self._ws_bytes, stream)
 
     def download(self, stream: int) -> None:
         """Both counts first, then only the counted bytes; synchronizes `stream` twice."""
-        if self.vertices is None:
-            raise RuntimeError("DeviceMesh already freed")
+        self._live()
         s = C.c_void_p(int(stream or 0))
         if not self.faces:
             self.counts.host[self.batch:] = 0
@@ -778,8 +759,7 @@ class DeviceMesh:
 
     def result(self):
         """One (vertices, faces) pair of views per image; valid after download()."""
-        if self.vertices is None:
-            raise RuntimeError("DeviceMesh already freed")
+        self._live()
         out = []
         for b in range(self.batch):
             nv, nf = int(self.counts.host[b]), int(self.counts.host[self.batch + b])
@@ -788,27 +768,6 @@ class DeviceMesh:
                  .view(FACE_DTYPE) if self.faces else np.zeros(0, FACE_DTYPE))
             out.append((v, f))
         return out
-
-    def run(self, d_depth: int, stream: int, **kw):
-        self.enqueue(d_depth, stream, **kw)
-        self.download(stream)
-        return self.result()
-
-    def free(self) -> None:
-        for m in (self.vertices, self.face_records, self.counts):
-            if m is not None:
-                m.free()
-        self.vertices = self.face_records = self.counts = None
-        if self._ws:
-            _lib.call("mde_rt_free", C.c_void_p(self._ws))
-            self._ws = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
 
 
 def mesh_header(vertex_count: int, face_count: int, colour: bool) -> bytes:
@@ -863,47 +822,22 @@ def read_ply_mesh(path):
 
 def device_mesh(path, d_depth: int, h: int, w: int, stream: int, step: int = 1, img_bgr: Optional[np.ndarray] = None,
                 d_f_px: int = 0, f_px: Optional[float] = None, z_lo: float = 1e-4, z_hi: float = 1e4,
-                edge_rtol: float = EDGE_RTOL, edge_atol: float = 0.0, faces: bool = True):
+                edge_rtol: float = EDGE_RTOL, edge_atol: float = 0.0, faces: bool = True, d_photo: int = 0):
     """What the model drivers' --mesh does (and, with `faces` off, --ply with
     --ply-edge-rtol): DeviceMesh on one device depth map [h][w] at `d_depth`,
     camera and colours as for `device_ply`, written to `path` (a mesh PLY, or
     with `faces` off write_ply's vertex-only file).  Returns (ms of the kernels
     + D2H between two hipEvents on `stream`, vertices, triangles)."""
-    if img_bgr is not None and (img_bgr.dtype != np.uint8 or img_bgr.shape != (h, w, 3)):
-        raise ValueError(f"the photo must be uint8 [{h}, {w}, 3], got {img_bgr.dtype} {img_bgr.shape}")
-    s = C.c_void_p(int(stream or 0))
-    photo = None
-    ev = [C.c_void_p(), C.c_void_p()]
-    try:
-        for e in ev:
-            _lib.call("mde_rt_event_create", C.byref(e))
-        if img_bgr is not None:
-            photo = HostDeviceMem(h * w * 3, np.uint8)
-            photo.host = np.ascontiguousarray(img_bgr).reshape(-1)
-            _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(photo.device), photo.host.ctypes.data_as(C.c_void_p),
-                      photo.nbytes, s)
-        with DeviceMesh(1, h, w, colour=photo is not None, step=step, faces=faces) as mesh:
-            _lib.call("mde_rt_event_record", ev[0], s)
-            mesh.enqueue(d_depth, stream, d_photo=photo.device if photo else 0, pitch=3 * w, swap_rb=True,
-                         d_f_px=0 if f_px is not None else d_f_px, fx=f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=edge_rtol,
-                         edge_atol=edge_atol)
-            mesh.download(stream)
-            _lib.call("mde_rt_event_record", ev[1], s)
-            stream_synchronize(stream)
-            vertices, tri = mesh.result()[0]
-            if faces:
-                write_ply_mesh(path, vertices, tri)
-            else:
-                write_ply(path, vertices)
-            ms = C.c_float()
-            _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
-            return float(ms.value), int(vertices.shape[0]), int(tri.shape[0])
-    finally:
-        if photo is not None:
-            photo.free()
-        for e in ev:
-            if e:
-                _lib.call("mde_rt_event_destroy", e)
+    with _device_photo(img_bgr, d_photo, h, w, stream) as d_photo, \
+            DeviceMesh(1, h, w, colour=bool(d_photo), step=step, faces=faces) as mesh:
+        ms = _timed(mesh, d_depth, stream, d_photo, d_f_px, f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=edge_rtol,
+                    edge_atol=edge_atol)
+        vertices, tri = mesh.result()[0]
+        if faces:
+            write_ply_mesh(path, vertices, tri)
+        else:
+            write_ply(path, vertices)
+        return ms, int(vertices.shape[0]), int(tri.shape[0])
 
 
 def add_mesh_arguments(ap) -> None:
@@ -934,28 +868,104 @@ def check_mesh_arguments(a) -> None:
             raise SystemExit("--ply-edge-rtol must not be negative")
 
 
-def driver_mesh(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, z_lo=1e-4, z_hi=1e4):
+def driver_mesh(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, z_lo=1e-4, z_hi=1e4,
+                d_photo: int = 0):
     """The drivers' --mesh: the mesh of the device map [hw] at `d_depth` and
     its `[MDET] mesh ...` line.  Returns (vertices, triangles)."""
     ms, nv, nf = device_mesh(a.mesh, d_depth, hw[0], hw[1], stream, step=a.mesh_step, img_bgr=img_bgr, d_f_px=d_f_px,
-                             f_px=f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=a.edge_rtol, edge_atol=a.edge_atol)
+                             f_px=f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=a.edge_rtol, edge_atol=a.edge_atol,
+                             d_photo=d_photo)
     print(f"[MDET] mesh (device, kernels + D2H, hipEvents) {hw[0]}x{hw[1]} step {a.mesh_step} rtol {a.edge_rtol:g} "
           f"atol {a.edge_atol:g} -> {a.mesh} : {ms:0.3f} ms, {nv} vertices, {nf} triangles")
     return nv, nf
 
 
-def driver_ply(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, z_lo=1e-4, z_hi=1e4):
+def driver_ply(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, z_lo=1e-4, z_hi=1e4,
+               d_photo: int = 0):
     """The drivers' --ply: `device_ply`, or with --ply-edge-rtol the
-    edge-filtered cloud of `device_mesh`; (ms, points)."""
+    edge-filtered cloud of `device_mesh`, and its `[MDET] point cloud ...`
+    line.  Returns (ms, points)."""
+    kw = dict(step=a.ply_step, img_bgr=img_bgr, d_f_px=d_f_px, f_px=f_px, z_lo=z_lo, z_hi=z_hi, d_photo=d_photo)
     if a.ply_edge_rtol is None:
-        return device_ply(a.ply, d_depth, hw[0], hw[1], stream, step=a.ply_step, img_bgr=img_bgr, d_f_px=d_f_px,
-                          f_px=f_px, z_lo=z_lo, z_hi=z_hi)
-    return device_mesh(a.ply, d_depth, hw[0], hw[1], stream, step=a.ply_step, img_bgr=img_bgr, d_f_px=d_f_px,
-                       f_px=f_px, z_lo=z_lo, z_hi=z_hi, edge_rtol=a.ply_edge_rtol, faces=False)[:2]
+        ms, n = device_ply(a.ply, d_depth, hw[0], hw[1], stream, **kw)
+    else:
+        ms, n = device_mesh(a.ply, d_depth, hw[0], hw[1], stream, edge_rtol=a.ply_edge_rtol, faces=False, **kw)[:2]
+    print(f"[MDET] point cloud (device, kernels + D2H, hipEvents) {hw[0]}x{hw[1]} step {a.ply_step} -> {a.ply} : "
+          f"{ms:0.3f} ms, {n} points")
+    return ms, n
+
+
+def _asked(a):
+    """Those of --ply, --mesh and --cloud-view that the parsed arguments ask for, in the order they run."""
+    return [opt for opt, path in (("--ply", a.ply), ("--mesh", a.mesh), ("--cloud-view", a.cloud_view)) if path]
+
+
+def add_cloud_arguments(ap, needs_f_px: bool = False) -> None:
+    """The drivers' cloud outputs: --ply, --mesh and --cloud-view with their
+    options (the module's docstring describes them)."""
+    ap.add_argument("--ply", default="", metavar="PATH",
+                    help="write the point cloud (binary PLY; colours from --image) of the metric depth"
+                         + ("; needs --f-px" if needs_f_px else ""))
+    ap.add_argument("--ply-step", type=int, default=1, help="with --ply: keep every N-th pixel on both axes")
+    add_mesh_arguments(ap)
+    add_cloud_view_arguments(ap)
+
+
+def check_cloud_arguments(a, needs_f_px: bool = False, metric: bool = True, no_device_map: str = "") -> None:
+    """What can be refused without a device, option by option: first whether
+    this driver can serve it -- `needs_f_px`: the model predicts no focal
+    length, so --f-px is required; `metric` off: a relative model (a driver
+    asks again with what the opened engine says); `no_device_map`: why there is
+    no device depth map to run on, if there is none -- then the option's own
+    values."""
+    def servable(opt):
+        if needs_f_px and (a.f_px is None or not a.f_px > 0):
+            raise SystemExit(f"{opt} needs --f-px (a positive focal length in pixels): this model predicts none")
+        if not metric:
+            raise SystemExit(f"{opt} needs a metric model: relative depth is not turned into metres")
+        if no_device_map:
+            raise SystemExit(f"{opt} runs on the device post-process's depth map: {no_device_map}")
+
+    if a.ply:
+        servable("--ply")
+        if a.ply_step < 1:
+            raise SystemExit("--ply-step must be positive")
+    if a.mesh:
+        servable("--mesh")
+    check_mesh_arguments(a)
+    if a.cloud_view:
+        servable("--cloud-view")
+    check_cloud_view_arguments(a)
+
+
+def check_photo_size(a, img_bgr, hw) -> None:
+    """The colours come from the --image photo: the map must have its size."""
+    asked = _asked(a)
+    if asked and img_bgr is not None and tuple(hw) != img_bgr.shape[:2]:
+        raise SystemExit(f"{asked[0]} takes its colours from the --image photo: --src-hw must be the photo's size")
+
+
+def run_cloud_outputs(a, d_depth: int, hw, stream: int, img_bgr=None, d_f_px: int = 0, f_px=None, z_lo=1e-4,
+                      z_hi=1e4) -> None:
+    """The drivers' --ply, --mesh and --cloud-view, in this order, on the
+    device map [hw] at `d_depth`, with the given `f_px` or else the device
+    focal length `d_f_px`; `z_lo`, `z_hi`: the driver's clamp.  The photo is
+    uploaded once for all of them."""
+    if not _asked(a):
+        return
+    with _device_photo(img_bgr, 0, hw[0], hw[1], stream) as d_photo:
+        kw = dict(d_f_px=d_f_px, f_px=f_px, d_photo=d_photo)
+        if a.ply:
+            driver_ply(a, d_depth, hw, stream, z_lo=z_lo, z_hi=z_hi, **kw)
+        if a.mesh:
+            driver_mesh(a, d_depth, hw, stream, z_lo=z_lo, z_hi=z_hi, **kw)
+        if a.cloud_view:
+            driver_cloud_view(a, d_depth, hw, stream, **kw)
 
 
 __all__ = ["vertex_dtype", "grid", "unproject_np", "ws_bytes", "point_cloud", "DevicePointCloud", "device_ply", "ply_header",
            "write_ply", "read_ply", "view_trig", "render_np", "cloud_view_ws_bytes", "cloud_view", "DeviceCloudView",
            "device_cloud_view", "add_cloud_view_arguments", "check_cloud_view_arguments", "driver_cloud_view",
            "FACE_DTYPE", "mesh_np", "mesh_ws_bytes", "depth_mesh", "DeviceMesh", "mesh_header", "write_ply_mesh",
-           "read_ply_mesh", "device_mesh", "add_mesh_arguments", "check_mesh_arguments", "driver_mesh", "driver_ply"]
+           "read_ply_mesh", "device_mesh", "add_mesh_arguments", "check_mesh_arguments", "driver_mesh", "driver_ply",
+           "add_cloud_arguments", "check_cloud_arguments", "check_photo_size", "run_cloud_outputs"]

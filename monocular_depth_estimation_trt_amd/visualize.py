@@ -29,7 +29,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _lib, colormaps
-from .common_runtime import HostDeviceMem, stream_synchronize
+from .common_runtime import EventPair, HostDeviceMem, stream_synchronize
 from .preprocess import resize_u8
 
 MODES = ("inverse_auto", "minmax_u8", "fixed")
@@ -570,39 +570,32 @@ def device_color(d_map: int, h: int, w: int, stream: int, mode, resize_hw=None, 
     Mode "robust" with `d_range` (DeviceColorize.enqueue) reports `range_host`."""
     range_host = kw.pop("range_host", None)
     s = C.c_void_p(int(stream or 0))
-    ev = [C.c_void_p(), C.c_void_p()]
     big = None
     try:
-        for e in ev:
-            _lib.call("mde_rt_event_create", C.byref(e))
         with DeviceColorize(1, h, w) as dc:
             if resize_hw is not None:
                 H, W = int(resize_hw[0]), int(resize_hw[1])
                 big = HostDeviceMem(H * W * 3, np.uint8)
-            _lib.call("mde_rt_event_record", ev[0], s)
-            dc.enqueue(d_map, stream, mode, **kw)
-            if big is None:
-                dc.download(stream)
-            else:
-                resize_u8(dc.out.device, 1, h, w, 3 * w, False, big.device, H, W, stream)
-                if mode == "robust" and not kw.get("d_range"):
-                    dc.quant.download(stream)
-                for m in (big,) if mode == "robust" else (big, dc.rng):
-                    _lib.call("mde_rt_memcpy_dtoh_async", m.host.ctypes.data_as(C.c_void_p), C.c_void_p(m.device),
-                              m.nbytes, s)
-            _lib.call("mde_rt_event_record", ev[1], s)
-            stream_synchronize(stream)
-            ms = C.c_float()
-            _lib.call("mde_rt_event_elapsed_ms", C.byref(ms), ev[0], ev[1])
+            with EventPair(stream) as ev:
+                dc.enqueue(d_map, stream, mode, **kw)
+                if big is None:
+                    dc.download(stream)
+                else:
+                    resize_u8(dc.out.device, 1, h, w, 3 * w, False, big.device, H, W, stream)
+                    if mode == "robust" and not kw.get("d_range"):
+                        dc.quant.download(stream)
+                    for m in (big,) if mode == "robust" else (big, dc.rng):
+                        _lib.call("mde_rt_memcpy_dtoh_async", m.host.ctypes.data_as(C.c_void_p),
+                                  C.c_void_p(m.device), m.nbytes, s)
+                ev.stop()
+                stream_synchronize(stream)
+                ms = ev.ms()
             lo, hi = range_host if range_host is not None else dc.range()[0]
             pic = dc.result()[0].copy() if big is None else big.host.reshape(H, W, 3).copy()
-            return float(ms.value), pic, (float(lo), float(hi))
+            return ms, pic, (float(lo), float(hi))
     finally:
         if big is not None:
             big.free()
-        for e in ev:
-            if e:
-                _lib.call("mde_rt_event_destroy", e)
 
 
 def device_distribution(d_map: int, h: int, w: int, stream: int) -> Optional[dict]:
