@@ -765,6 +765,41 @@ int mde_op_resize_cubic_u8_norm(const unsigned char* src, int batch, int sh, int
                                 void* stream);
 int mde_op_crop_f32(const float* src, int batch, int h, int w, int y0, int x0, int ch, int cw, float* dst,
                     void* stream);
+/* DA-V2 family native profile (added to ABI 11 without a new version number, as the additions before it):
+ * the input half of reference models/depth_anything_ac/onnx2trt.py's `native` profile over core/preprocess.py
+ * (preprocess_for(img, model, size, stretch=False)): cvtColor(BGR2RGB), no first resize, /255 in T, ONE
+ * cv2.resize(INTER_CUBIC) of the FLOAT image to the keep-ratio size (preprocess.py:native_size), standardise
+ * in float64, float32 NCHW -- read straight from the uint8 photo; the float image is never materialised.
+ * It restates OpenCV's published SCALAR INTER_CUBIC for CV_32FC3 (wide == 0, T = float: depth_anything_ac)
+ * and CV_64FC3 (wide == 1, T = double: depth_anything_v2); parity with cv2 itself is not pinned in this
+ * repository ("Native profile": vectorised builds nest the float32 vertical pass as multiply-adds
+ * in the opposite order, IPP builds replace the routine; both can differ in the last bit of a float32), the
+ * kernel is pinned bit for bit to monocular_depth_estimation_trt_amd/preprocess.py:resize_cubic_float plus
+ * the standardise.  The contract:
+ *   per axis: scale, f, s, x, the taps s - 1 .. s + 2 clamped to [0, src - 1] and the float32 coefficients
+ *   c0 .. c3 exactly as for mde_op_resize_cubic_u8 above (no pad: the virtual image is the photo); the
+ *   coefficients stay float32, there is no rint(c * 2048)
+ *   sample: S = scale_lut[u], scale_lut a device T[256] the caller filled with (T)u / (T)255
+ *   horizontal pass, a_i the column coefficients, each product and each sum rounded once in T, left to right
+ *   (a float32 coefficient times a float64 sample is a float64 product), never fused
+ *     H = ((S[t0]*a0 + S[t1]*a1) + S[t2]*a2) + S[t3]*a3
+ *   vertical pass, b_j the row coefficients, the same discipline; no clamp, cubic overshoot outside [0, 1] stays
+ *     V = ((H0*b0 + H1*b1) + H2*b2) + H3*b3
+ *   out[c] = (float)(((double)V[c] - mean_c) / std_c)      float64, rounded once to float32
+ * src is [batch][sh][pitch] bytes with the rules of mde_op_resize_u8 (3 interleaved channels per pixel,
+ * pitch >= 3 * sw, bytes of a row past 3 * sw are never read, swap_rb != 0 writes source channel 2 - c to
+ * output channel c); mean0..2 / std0..2 are in OUTPUT channel order; dst is float32 NCHW [batch][3][oh][ow]
+ * (the engine's "input" binding).  Only enqueues one kernel on `stream` (no allocation, no synchronisation:
+ * capturable); nothing is written outside the destination.  MDE_ERR_ARG, before any device call: a null
+ * pointer; a non-positive size; pitch < 3 * sw; wide not 0 or 1; scale_lut not aligned to T or dst not to 4
+ * bytes; a NaN mean; a zero or NaN std; a source or destination plane of 2^31 - 256 elements or more;
+ * batch > 65535. */
+int mde_op_resize_cubic_f_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb,
+                               int wide,                       /* 0: T = float, 1: T = double */
+                               const void* scale_lut,          /* device T[256]: (T)u / (T)255, made on the host */
+                               double mean0, double mean1, double mean2,   /* output channel order */
+                               double std0, double std1, double std2,
+                               float* dst, int oh, int ow, void* stream);  /* dst: [batch][3][oh][ow] */
 /* Depth Pro pyramid patches (upstream DepthProEncoder._create_pyramid + _split, reference engine input
  * "input"): fp32 NCHW image [batch][3][size][size] (size = 4 * 384) -> f16 patch-embed rows
  * [nseq * batch * 576][768] ((c, py, px) order), sequence s = patch * batch + image with the 25

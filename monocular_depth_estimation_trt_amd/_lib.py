@@ -198,6 +198,8 @@ PROTOTYPES = {
     "mde_op_resize_cubic_u8": [c_void_p] + [c_int] * 12 + [c_void_p, c_int, c_int, c_void_p],
     "mde_op_resize_cubic_u8_norm": [c_void_p] + [c_int] * 12 + [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "mde_op_crop_f32": [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p],
+    "mde_op_resize_cubic_f_norm": [c_void_p] + [c_int] * 6 + [c_void_p] + [C.c_double] * 6 + [c_void_p, c_int, c_int,
+                                                                                          c_void_p],
     "mde_op_qk_norm_rope": [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_void_p, c_float, c_float, c_void_p],
     "mde_op_tap_concat_ln": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p,
                              c_void_p],

@@ -309,6 +309,12 @@ hipError_t launch_resize_cubic_u8(const unsigned char* src, int B, int sh, int s
                                   const float* lut, void* dst, int oh, int ow, hipStream_t st);
 hipError_t launch_crop_f32(const float* src, int B, int h, int w, int y0, int x0, int ch, int cw, float* dst,
                            hipStream_t st);
+// preprocess_cubic.hip: cv2's scalar float INTER_CUBIC of the photo / 255 in T = float (wide == 0) or
+// double, then (x - mean) / std in float64, rounded once to float32 NCHW [B][3][oh][ow] (include/mde.h,
+// mde_op_resize_cubic_f_norm); lut: device T[256], mean / stdv in output channel order.  One kernel
+hipError_t launch_resize_cubic_f_norm(const unsigned char* src, int B, int sh, int sw, int pitch, int swap_rb,
+                                      int wide, const void* lut, const double mean[3], const double stdv[3],
+                                      float* dst, int oh, int ow, hipStream_t st);
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H,
                              int W, int ph, int pw, int T, int D, hipStream_t st, h16* Xh = nullptr,
                              float* lnst = nullptr, const float* cls_st = nullptr, float* P32 = nullptr);

@@ -386,6 +386,24 @@ int mde_op_resize_cubic_u8_norm(const unsigned char* src, int batch, int sh, int
          "mde_op_resize_cubic_u8_norm");
 }
 
+int mde_op_resize_cubic_f_norm(const unsigned char* src, int batch, int sh, int sw, int pitch, int swap_rb, int wide,
+                               const void* scale_lut, double mean0, double mean1, double mean2, double std0,
+                               double std1, double std2, float* dst, int oh, int ow, void* st) {
+  const char* why = resize_cubic_arg_error(src, dst, batch, sh, sw, pitch, 0, 0, 0, 0, 0, 0, 0, oh, ow);
+  if (!why && !scale_lut) why = "null pointer";
+  if (!why && wide != 0 && wide != 1) why = "wide must be 0 (float) or 1 (double)";
+  if (!why && (reinterpret_cast<uintptr_t>(scale_lut) & (wide ? 7 : 3))) why = "scale_lut is not aligned to its type";
+  if (!why && (reinterpret_cast<uintptr_t>(dst) & 3)) why = "dst must be 4-byte aligned";
+  if (!why && !(mean0 == mean0 && mean1 == mean1 && mean2 == mean2)) why = "a NaN mean";
+  for (double s : {std0, std1, std2})
+    if (!why && (s == 0.0 || s != s)) why = "a zero or NaN std";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_resize_cubic_f_norm: ") + why);
+  const double mean[3] = {mean0, mean1, mean2}, stdv[3] = {std0, std1, std2};
+  OP_RET(launch_resize_cubic_f_norm(src, batch, sh, sw, pitch, swap_rb, wide, scale_lut, mean, stdv, dst, oh, ow,
+                                    (hipStream_t)st),
+         "mde_op_resize_cubic_f_norm");
+}
+
 int mde_op_crop_f32(const float* src, int batch, int h, int w, int y0, int x0, int ch, int cw, float* dst, void* st) {
   const char* why = nullptr;
   if (!src || !dst) why = "null pointer";

@@ -64,6 +64,23 @@
 // border coordinate.  48 byte loads and 3 bytes or 3 floats stored per thread;
 // 268 324 threads at 518^2.
 //
+// resize_cubic_f_norm_kernel<T>: the DA-V2 family's native profile, the
+// reference's keep-ratio cubic resize of the FLOAT image (core/preprocess.py:
+// scale, then ResizeStep("keep_ratio", interp="cubic"), then standardize), read
+// straight from the uint8 photo.  The same positions, taps and float32
+// coefficients as above (coef4), kept as float32 instead of rounded to 1 / 2048;
+// samples T(u) / T(255) from a host-made table; both passes in T = float or
+// double, one rounding per product and per sum, left to right; no clamp; then
+// (V - mean) / std in float64 and one rounding to float32.  The contract is in
+// include/mde.h at mde_op_resize_cubic_f_norm; preprocess.py:resize_cubic_float
+// is the numpy restatement the tests hold it to, bit for bit.  Same thread
+// mapping and byte loads as the 8-bit kernel, no image tile in LDS: at
+// 3024 -> 700 neighbouring outputs share no tap; at ratios near 1 (640 -> 700)
+// they share three of four columns and all four rows, and those repeats hit L1
+// / L2 (a wave's 64 outputs of one row touch about 4 x 190 contiguous bytes).
+// The table is the one thing every thread reads 48 times, so it alone goes to
+// LDS (1 or 2 KB per block).
+//
 // crop_f32_kernel: one thread per destination element, a strided row copy.
 
 #include <hip/hip_runtime.h>
@@ -75,28 +92,40 @@
 namespace mde {
 namespace {
 
+struct Coef4 {
+  int s;       // first tap, s - 1 of the contract, unclamped
+  float c[4];  // float32 weights
+};
+
+// position, taps and coefficients of output index d: what the 8-bit and the float resize share
+__device__ __forceinline__ Coef4 coef4(int d, double scale) {
+  const double pos = __dadd_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), -0.5);
+  const float f = __double2float_rn(pos);
+  const float fl = floorf(f);
+  const float x = __fsub_rn(f, fl);
+  constexpr float A = -0.75f;
+  Coef4 t;
+  const float x1 = __fadd_rn(x, 1.f);
+  t.c[0] = __fsub_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(A, x1), 5 * A), x1), 8 * A), x1), 4 * A);
+  t.c[1] = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(A + 2, x), A + 3), x), x), 1.f);
+  const float g = __fsub_rn(1.f, x);
+  t.c[2] = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(A + 2, g), A + 3), g), g), 1.f);
+  t.c[3] = __fsub_rn(__fsub_rn(__fsub_rn(1.f, t.c[0]), t.c[1]), t.c[2]);
+  t.s = (int)fl - 1;
+  return t;
+}
+
 struct Tap4 {
   int s;     // first tap, s - 1 of the contract, unclamped
   int k[4];  // 11-bit fixed-point weights
 };
 
 __device__ __forceinline__ Tap4 tap4(int d, double scale) {
-  const double pos = __dadd_rn(__dmul_rn(__dadd_rn((double)d, 0.5), scale), -0.5);
-  const float f = __double2float_rn(pos);
-  const float fl = floorf(f);
-  const float x = __fsub_rn(f, fl);
-  constexpr float A = -0.75f;
-  float c[4];
-  const float x1 = __fadd_rn(x, 1.f);
-  c[0] = __fsub_rn(__fmul_rn(__fadd_rn(__fmul_rn(__fsub_rn(__fmul_rn(A, x1), 5 * A), x1), 8 * A), x1), 4 * A);
-  c[1] = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(A + 2, x), A + 3), x), x), 1.f);
-  const float g = __fsub_rn(1.f, x);
-  c[2] = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(A + 2, g), A + 3), g), g), 1.f);
-  c[3] = __fsub_rn(__fsub_rn(__fsub_rn(1.f, c[0]), c[1]), c[2]);
+  const Coef4 q = coef4(d, scale);
   Tap4 t;
-  t.s = (int)fl - 1;
+  t.s = q.s;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) t.k[i] = __float2int_rn(__fmul_rn(c[i], 2048.f));
+  for (int i = 0; i < 4; ++i) t.k[i] = __float2int_rn(__fmul_rn(q.c[i], 2048.f));
   return t;
 }
 
@@ -166,6 +195,60 @@ resize_cubic_u8_kernel(const unsigned char* __restrict__ src, CubicGeom g, int s
   }
 }
 
+struct CubicFGeom {
+  int sh, sw, pitch;
+  double scale_y, scale_x;
+  double mean[3], std[3];  // in SOURCE channel order
+};
+
+// The DA-V2 family's native profile (include/mde.h, mde_op_resize_cubic_f_norm): cv2's scalar float
+// INTER_CUBIC of the photo after its division by 255, working type T, then the standardise in float64
+// and one rounding to float32.  T(u) / T(255) comes from a 256-entry table the host made; the block
+// copies it to LDS once (one entry per thread), so the 48 lookups of a thread are LDS reads and the
+// vector memory path carries the byte taps alone.
+template <typename T>
+__global__ void __launch_bounds__(256)
+resize_cubic_f_norm_kernel(const unsigned char* __restrict__ src, CubicFGeom g, int swap_rb,
+                           const T* __restrict__ lut, float* __restrict__ dst, int oh, int ow) {
+  __shared__ T lut_s[256];
+  lut_s[threadIdx.x] = lut[threadIdx.x];  // blockDim.x == 256
+  __syncthreads();
+  const int plane = oh * ow;  // the ABI wrapper keeps it below 2^31 - 256
+  const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int b = (int)blockIdx.y;
+  if (r >= plane) return;  // after the only barrier
+  const int oy = r / ow, ox = r - oy * ow;
+  const unsigned char* img = src + (size_t)b * g.sh * g.pitch;
+  const Coef4 tx = coef4(ox, g.scale_x);
+  const Coef4 ty = coef4(oy, g.scale_y);
+
+  int off[4];  // byte offset of the tap's pixel in a row, clamped into the photo
+#pragma unroll
+  for (int i = 0; i < 4; ++i) off[i] = 3 * min(max(tx.s + i, 0), g.sw - 1);
+  T v[3];  // in source channel order
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const unsigned char* row = img + (size_t)min(max(ty.s + j, 0), g.sh - 1) * g.pitch;
+    const T bj = (T)ty.c[j];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      // H = ((S0 a0 + S1 a1) + S2 a2) + S3 a3, each product and sum rounded once in T
+      T h = lut_s[row[off[0] + c]] * (T)tx.c[0];
+      h = h + lut_s[row[off[1] + c]] * (T)tx.c[1];
+      h = h + lut_s[row[off[2] + c]] * (T)tx.c[2];
+      h = h + lut_s[row[off[3] + c]] * (T)tx.c[3];
+      // V = ((H0 b0 + H1 b1) + H2 b2) + H3 b3, the same discipline
+      const T p = h * bj;
+      v[c] = j == 0 ? p : v[c] + p;
+    }
+  }
+  float* o = dst + (size_t)b * 3 * plane + r;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)  // source channel c is output channel 2 - c under swap_rb
+    o[(size_t)(swap_rb ? 2 - c : c) * plane] =
+        __double2float_rn(__ddiv_rn(__dsub_rn((double)v[c], g.mean[c]), g.std[c]));
+}
+
 __global__ void __launch_bounds__(256)
 crop_f32_kernel(const float* __restrict__ src, int h, int w, int y0, int x0, int ch, int cw,
                 float* __restrict__ dst) {
@@ -200,6 +283,30 @@ hipError_t launch_resize_cubic_u8(const unsigned char* src, int B, int sh, int s
     hipLaunchKernelGGL(resize_cubic_u8_kernel<true>, grid, block, 0, st, src, g, swap_rb, lut, dst, oh, ow);
   else
     hipLaunchKernelGGL(resize_cubic_u8_kernel<false>, grid, block, 0, st, src, g, swap_rb, lut, dst, oh, ow);
+  return hipGetLastError();
+}
+
+hipError_t launch_resize_cubic_f_norm(const unsigned char* src, int B, int sh, int sw, int pitch, int swap_rb,
+                                      int wide, const void* lut, const double mean[3], const double stdv[3],
+                                      float* dst, int oh, int ow, hipStream_t st) {
+  CubicFGeom g;
+  g.sh = sh;
+  g.sw = sw;
+  g.pitch = pitch;
+  g.scale_x = 1.0 / ((double)ow / (double)sw);
+  g.scale_y = 1.0 / ((double)oh / (double)sh);
+  for (int c = 0; c < 3; ++c) {  // given in output channel order
+    g.mean[swap_rb ? 2 - c : c] = mean[c];
+    g.std[swap_rb ? 2 - c : c] = stdv[c];
+  }
+  const long long plane = (long long)oh * ow;
+  const dim3 grid((unsigned)((plane + 255) / 256), (unsigned)B), block(256);
+  if (wide)
+    hipLaunchKernelGGL(resize_cubic_f_norm_kernel<double>, grid, block, 0, st, src, g, swap_rb,
+                       static_cast<const double*>(lut), dst, oh, ow);
+  else
+    hipLaunchKernelGGL(resize_cubic_f_norm_kernel<float>, grid, block, 0, st, src, g, swap_rb,
+                       static_cast<const float*>(lut), dst, oh, ow);
   return hipGetLastError();
 }
 

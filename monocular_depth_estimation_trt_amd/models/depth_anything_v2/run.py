@@ -10,7 +10,7 @@ onnx2trt.py` (the same ViT-S DA-V2 graph, relative head), same sequence:
 
     python -m monocular_depth_estimation_trt_amd.models.depth_anything_v2.run \
         [--source synthetic:vits:metric | ckpt.pth] [--input x.npy] [--src-hw H W]
-        [--image photo.npy|photo.jpg] [--host-preprocess]
+        [--image photo.npy|photo.jpg] [--host-preprocess] [--profile bench|native [--native-target N]]
         [--input-format float32_nchw | uint8_nhwc] [--host-postprocess]
         [--ply out.ply --f-px F [--ply-step N] [--ply-edge-rtol R]]
         [--mesh out.ply --f-px F [--mesh-step N] [--edge-rtol R] [--edge-atol A]]
@@ -25,6 +25,17 @@ stretch on uint8, /255, standardise) on the device, straight into the
 engine's input binding (preprocess.DevicePreprocess; `--host-preprocess`: the
 numpy version and the usual upload); `--src-hw` then defaults to the photo's
 own size.  The pre-process is outside the timed loop, as in the reference.
+`--profile native` (depth_anything_v2 and depth_anything_ac; reference
+models/depth_anything_ac/onnx2trt.py:50-77) does not stretch the photo to the
+engine's square: the engine is built for preprocess.native_size of the photo
+(short side `--native-target`, default 518, aspect kept, sides snapped to
+multiples of 14: 518x700 for a 4:3 photo under depth_anything_ac's rule,
+518x686 under depth_anything_v2's) and the photo reaches it through the
+reference's keep-ratio cubic resize of the float image, on the device
+(preprocess.NativePreprocess) or with `--host-preprocess` in numpy
+(preprocess_native_host).  A default `--engine` path gets that size in its
+name, so bench and native engines coexist.  Everything after the engine runs
+unchanged on the source-size map.
 `--input` is an already-preprocessed float32 NCHW [1,3,518,518] tensor (the
 reference's core/preprocess.py needs cv2, absent here), or for
 `--input-format uint8_nhwc` the uint8 [1,518,518,3] image the reference's
@@ -72,8 +83,9 @@ import numpy as np
 from monocular_depth_estimation_trt_amd import bench, common, evaluate, spec, visualize, weights
 from monocular_depth_estimation_trt_amd import pointcloud
 from monocular_depth_estimation_trt_amd.postprocess import DevicePostprocess
-from monocular_depth_estimation_trt_amd.preprocess import (DevicePreprocess, load_image_bgr, preprocess_host,
-                                                           resize_linear_u8)
+from monocular_depth_estimation_trt_amd.preprocess import (NATIVE_ROUNDING, DevicePreprocess, NativePreprocess,
+                                                           load_image_bgr, native_size, preprocess_host,
+                                                           preprocess_native_host, resize_linear_u8)
 from monocular_depth_estimation_trt_amd.common_runtime import (EventPair, allocate_buffers, do_inference,
                                                                free_buffers, hip_call, stream_synchronize)
 
@@ -100,6 +112,10 @@ def build_parser(model="depth_anything_v2", mc=None):
     ap.add_argument("--image", default="", help="source-resolution BGR photo: .npy (uint8 [H,W,3]) or an image file")
     ap.add_argument("--host-preprocess", action="store_true",
                     help="with --image: pre-process on the host (numpy) and upload, instead of on the device")
+    ap.add_argument("--profile", choices=("bench", "native"), default="bench",
+                    help="bench: stretch the photo to the engine's size; native: keep its aspect ratio (short side "
+                         "--native-target, multiples of 14) and build the engine for that size")
+    ap.add_argument("--native-target", type=int, default=518, help="with --profile native: the short side")
     ap.add_argument("--src-hw", type=int, nargs=2, default=None,
                     help="size of the returned map (default: the --image's own size, else 2268 3024)")
     ap.add_argument("--iterations", type=int, default=100)
@@ -124,13 +140,41 @@ def _check_cloud(a, mc, metric):
         no_device_map="not with --host-postprocess or a model without a post-process" if no_map else "")
 
 
-def _device_preprocess(img, model, input_hw, input_format, mem, stream):
-    """DevicePreprocess into the engine's input binding `mem.device`, timed with
-    hipEvents (H2D of the frame + the kernel); the pinned side of the binding
-    gets the same bytes back, so the timed loop's upload is a no-op in value."""
+def _check_native(a, model):
+    """--profile native's refusals, before the photo is opened."""
+    if a.input:
+        raise SystemExit("--profile native does not take --input: an already-preprocessed tensor has no photo to "
+                         "take the size rule from")
+    if not a.image:
+        raise SystemExit("--profile native needs --image: the engine's size follows the photo's")
+    if a.input_format == "uint8_nhwc":
+        raise SystemExit("--profile native does not take --input-format uint8_nhwc: the rule resizes the float "
+                         "image after its division by 255, and a uint8 engine normalises after the resize")
+    if model not in NATIVE_ROUNDING:
+        raise SystemExit(f"--profile native is not for {model}: its second resize stage snaps to the engine's size, "
+                         f"it has no keep-ratio rule (have {sorted(NATIVE_ROUNDING)})")
+    if a.native_target < 1:
+        raise SystemExit("--native-target must be positive")
+
+
+def native_engine_path(model, engine, default, input_hw):
+    """The default engine path with the native size in place of the spec's; a path the user gave stays."""
+    if engine != default:
+        return engine
+    mc = spec.model_config_of(spec.load(model))
+    return os.path.join(os.path.dirname(default), f"{model}_{mc['encoder']}_{input_hw[0]}x{input_hw[1]}_fp16.mdeng")
+
+
+def _device_preprocess(img, model, input_hw, input_format, mem, stream, native_target=None):
+    """DevicePreprocess (native_target: NativePreprocess) into the engine's input
+    binding `mem.device`, timed with hipEvents (H2D of the frame + the kernel);
+    the pinned side of the binding gets the same bytes back, so the timed loop's
+    upload is a no-op in value."""
     import ctypes as C
-    with DevicePreprocess(img.shape[0], img.shape[1], *input_hw, model, output=input_format) as pre, \
+    with (NativePreprocess(img.shape[0], img.shape[1], model, target=native_target) if native_target else
+          DevicePreprocess(img.shape[0], img.shape[1], *input_hw, model, output=input_format)) as pre, \
             EventPair(stream) as ev:
+        assert pre.dst == tuple(input_hw)
         pre.run(img, mem.device, stream)
         ev.stop()
         hip_call("mde_rt_memcpy_dtoh_async", mem.host.ctypes.data_as(C.c_void_p), C.c_void_p(mem.device),
@@ -143,10 +187,14 @@ def main(argv=None, model="depth_anything_v2"):
     model_spec = spec.load(model)
     mc = spec.model_config_of(model_spec)
     input_h, input_w = mc["input_hw"]
-    a = build_parser(model, mc).parse_args(argv)
+    parser = build_parser(model, mc)
+    a = parser.parse_args(argv)
     u8 = a.input_format == "uint8_nhwc"
+    native = a.profile == "native"
     if a.image and a.input:
         raise SystemExit("--image and --input are exclusive")
+    if native:
+        _check_native(a, model)
     if a.host_preprocess and not a.image:
         raise SystemExit("--host-preprocess needs --image")
     fields = a.source.split(":")
@@ -155,6 +203,10 @@ def main(argv=None, model="depth_anything_v2"):
     gt_policy = evaluate.check_gt_arguments(a, model_spec, device_map=not a.host_postprocess)
     visualize.check_color_arguments(a, device_map=not a.host_postprocess)
     img = load_image_bgr(a.image) if a.image else None
+    if native:  # the engine's size follows the photo
+        input_h, input_w = native_size(model, img.shape[0], img.shape[1], a.native_target)
+        a.engine = native_engine_path(model, a.engine, parser.get_default("engine"), (input_h, input_w))
+    how = f"native, target {a.native_target}" if native else "bench"
     if a.src_hw is None:
         a.src_hw = list(img.shape[:2]) if img is not None else [2268, 3024]
     gt_hw = (input_h, input_w) if mc["postprocess"] == "none" else tuple(a.src_hw)  # the size of the scored map
@@ -165,8 +217,9 @@ def main(argv=None, model="depth_anything_v2"):
     if img is not None and a.host_preprocess:
         t0 = time.perf_counter()
         x = (resize_linear_u8(img[:, :, ::-1], input_h, input_w)[None] if u8
+             else preprocess_native_host(img, model, a.native_target)[0] if native
              else preprocess_host(img, model, (input_h, input_w))[0])
-        print(f"[MDET] preprocess (host, numpy) {img.shape[0]}x{img.shape[1]} -> {input_h}x{input_w} : "
+        print(f"[MDET] preprocess (host, numpy) [{how}] {img.shape[0]}x{img.shape[1]} -> {input_h}x{input_w} : "
               f"{(time.perf_counter() - t0) * 1e3:0.3f} ms")
     elif img is not None:
         x = None  # filled on the device, below
@@ -184,8 +237,9 @@ def main(argv=None, model="depth_anything_v2"):
         _check_cloud(a, mc, metric=engine.info.metric)
         inputs, outputs, bindings, stream = allocate_buffers(engine, output_shape, profile_idx=0)
         if x is None:
-            ms = _device_preprocess(img, model, (input_h, input_w), a.input_format, inputs[0], stream)
-            print(f"[MDET] preprocess (device, H2D + kernel, hipEvents) {img.shape[0]}x{img.shape[1]} -> "
+            ms = _device_preprocess(img, model, (input_h, input_w), a.input_format, inputs[0], stream,
+                                    native_target=a.native_target if native else None)
+            print(f"[MDET] preprocess (device, H2D + kernel, hipEvents) [{how}] {img.shape[0]}x{img.shape[1]} -> "
                   f"{input_h}x{input_w} {a.input_format} : {ms:0.3f} ms")
             x = inputs[0].host[:3 * input_h * input_w].reshape(
                 (1, input_h, input_w, 3) if u8 else (1, 3, input_h, input_w)).copy()
@@ -212,7 +266,7 @@ def main(argv=None, model="depth_anything_v2"):
                     evaluate.driver_score(a, model, gt_policy, gt_maps, pp.mem.device, gt_hw, stream)
                 if a.color:
                     visualize.driver_color(a, model_spec, pp.mem.device, gt_hw, stream)
-        bench.record(model, samples, warmup=a.warmup, precision="fp16", profile="bench",
+        bench.record(model, samples, warmup=a.warmup, precision="fp16", profile=a.profile,
                      variant="u8" if u8 else "single",
                      input_h=input_h, input_w=input_w, engine_path=a.engine, outputs={"depth": depth},
                      encoder=mc["encoder"], notes=f"source={a.source}", model_input=x, out_dir=a.out_dir)

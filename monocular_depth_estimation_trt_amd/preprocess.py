@@ -14,7 +14,9 @@ bilinear interpolation.
 
 Depth Pro's pre-process is another function (normalise, then torch's float32
 bilinear) and has its own section further down; VGGT's (square pad with
-white, one cv2 INTER_CUBIC on uint8, /255) is the last section.
+white, one cv2 INTER_CUBIC on uint8, /255) follows it; the last section is the
+DA-V2 family's `native` profile (no stretch: a keep-ratio cv2 INTER_CUBIC on
+the float image, `preprocess_native_host` / `NativePreprocess`).
 """
 
 from __future__ import annotations
@@ -165,9 +167,10 @@ class _FramePreprocess:
         self.lut: Optional[HostDeviceMem] = None
         try:
             self.mem = HostDeviceMem(self.batch * self.src[0] * self.src[1] * 3, np.uint8)
-            if lut is not None:
-                self.lut = HostDeviceMem(lut.size, np.float32)
-                self.lut.host = np.ascontiguousarray(lut, dtype=np.float32)
+            if lut is not None:  # float32, or float64 where the subclass's kernel reads doubles
+                lut_dtype = np.float64 if lut.dtype == np.float64 else np.float32
+                self.lut = HostDeviceMem(lut.size, lut_dtype)
+                self.lut.host = np.ascontiguousarray(lut, dtype=lut_dtype)
                 _lib.call("mde_rt_memcpy_htod_async", C.c_void_p(self.lut.device),
                           self.lut.host.ctypes.data_as(C.c_void_p), self.lut.nbytes, None)
                 _lib.call("mde_rt_device_synchronize")
@@ -359,10 +362,11 @@ CUBIC_A = np.float32(-0.75)  # cv2's interpolateCubic
 VGGT_PAD = (255, 255, 255)   # core/preprocess.py:_builders().vggt pad_value
 
 
-def _axis_cubic(dst: int, src: int):
+def _axis_cubic_f32(dst: int, src: int):
     """Per output index of one axis: (taps int32 [4][dst], clamped to
-    [0, src - 1], weights int32 [4][dst]); float32 with one rounding per
-    operation, in the contract's order."""
+    [0, src - 1], coefficients float32 [4][dst]); float32 with one rounding
+    per operation, in the contract's order.  What the 8-bit and the float
+    cubic resize share."""
     f32 = np.float32
     scale = 1.0 / (float(dst) / float(src))  # float64; not src / dst
     pos = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
@@ -377,8 +381,16 @@ def _axis_cubic(dst: int, src: int):
     c3 = ((one - c0) - c1) - c2
     c = np.stack([c0, c1, c2, c3])
     assert c.dtype == np.float32
-    k = np.rint(c * f32(1 << COEF_BITS)).astype(np.int32)
     taps = np.clip(base.astype(np.int32)[None] + np.arange(-1, 3, dtype=np.int32)[:, None], 0, src - 1)
+    return taps, c
+
+
+def _axis_cubic(dst: int, src: int):
+    """Per output index of one axis: (taps int32 [4][dst], clamped to
+    [0, src - 1], weights int32 [4][dst]): _axis_cubic_f32's coefficients
+    rounded to multiples of 1 / 2048."""
+    taps, c = _axis_cubic_f32(dst, src)
+    k = np.rint(c * np.float32(1 << COEF_BITS)).astype(np.int32)
     return taps, k
 
 
@@ -507,8 +519,136 @@ class VggtPreprocess(_FramePreprocess):
                                self.dst[0], self.dst[1], stream, self.lut.device)
 
 
+# ---- DA-V2 family, native profile ---------------------------------------------
+# Reference models/depth_anything_ac/onnx2trt.py:50-77 (`profile = 'native'`)
+# over core/preprocess.py: preprocess_for(img, model, size, stretch=False) --
+# BGR->RGB, NO first resize, /255 in the model's scale dtype, then the second
+# geometry stage ResizeStep("keep_ratio", interp="cubic") on the FLOAT image
+# (short side to `target`, aspect kept, sides snapped to multiples of 14),
+# standardise in float64, float32 NCHW.  The contract is spelled out in
+# include/mde.h at mde_op_resize_cubic_f_norm; resize_cubic_float restates
+# OpenCV's published scalar INTER_CUBIC for CV_32FC3 / CV_64FC3 in numpy, one
+# rounding per operation in the contract's order, and the kernel
+# (csrc/preprocess_cubic.hip) is held to it bit for bit.  Parity with cv2
+# itself is not pinned (cv2 is not a dependency; DESIGN.md "Native profile"
+# says what that leaves open).
+
+NATIVE_ROUNDING = {"depth_anything_ac": "ceil", "depth_anything_v2": "constrain"}
+
+
+def native_size(model: str, src_h: int, src_w: int, target: int = 518, multiple: int = 14) -> Tuple[int, int]:
+    """(h, w) of the network input for a src_h x src_w photo: the reference's
+    resize_keep_ratio(bound="lower") over _round_to_multiple, in the same
+    float64 expressions (300 x 400 at target 42 gives h * scale =
+    42.00000000000001 and `ceil` makes 56 of it: reproduced, not corrected).
+    depth_anything_ac rounds up; depth_anything_v2 rounds half to even and
+    falls back to up where that lands below `target`."""
+    if model not in NATIVE_ROUNDING:
+        raise ValueError(f"{model} has no native size: its second resize stage is "
+                         f"{'a snap to the engine size' if model == 'distill_any_depth' else 'not declared'}, "
+                         f"not a keep-ratio rule (have {sorted(NATIVE_ROUNDING)})")
+    src_h, src_w, target, multiple = int(src_h), int(src_w), int(target), int(multiple)
+    if src_h < 1 or src_w < 1 or target < 1 or multiple < 1:
+        raise ValueError("native_size: sizes, target and multiple must be positive")
+    scale = target / min(src_h, src_w)  # float64
+
+    def snap(x: float) -> int:
+        q = x / multiple
+        if NATIVE_ROUNDING[model] == "ceil":
+            y = int(np.ceil(q)) * multiple
+        else:
+            y = int(np.round(q) * multiple)  # half to even
+            if y < target:
+                y = int(np.ceil(q) * multiple)
+        return max(y, multiple)
+
+    return snap(src_h * scale), snap(src_w * scale)
+
+
+def scale_lut(model: str) -> np.ndarray:
+    """T[256]: pixel value u after the reference's `scale`, u.astype(T) / 255.0
+    in the model's scale dtype T."""
+    return np.arange(256, dtype=np.uint8).astype(SCALE_DTYPE[model]) / 255.0
+
+
+def resize_cubic_float(img_hwc: np.ndarray, oh: int, ow: int) -> np.ndarray:
+    """`cv2.resize(img, (ow, oh), interpolation=cv2.INTER_CUBIC)` for a float32
+    or float64 [H, W, 3] image, dtype preserved: OpenCV's scalar algorithm with
+    _axis_cubic_f32's positions, taps and float32 coefficients, the horizontal
+    pass over whole rows first, then the vertical pass, every product and sum
+    rounded once in the image's dtype, left to right; no clamp."""
+    img = np.asarray(img_hwc)
+    if img.dtype not in (np.float32, np.float64) or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"resize_cubic_float wants a float32 or float64 [H, W, 3] image, got {img.dtype} {img.shape}")
+    oh, ow = int(oh), int(ow)
+    if oh < 1 or ow < 1 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("resize_cubic_float: sizes must be positive")
+    T = img.dtype
+    tx, a = _axis_cubic_f32(ow, img.shape[1])
+    ty, b = _axis_cubic_f32(oh, img.shape[0])
+    assert a.dtype == b.dtype == np.float32
+    # float32 * float32 stays float32; float64 * float32 is a float64 product (HResizeCubic<double, double, float>)
+    rows = img[:, tx[0]] * a[0][None, :, None]
+    for i in range(1, 4):
+        rows = rows + img[:, tx[i]] * a[i][None, :, None]
+    assert rows.dtype == T
+    out = rows[ty[0]] * b[0][:, None, None]
+    for j in range(1, 4):
+        out = out + rows[ty[j]] * b[j][:, None, None]
+    assert out.dtype == T
+    return out
+
+
+def preprocess_native_host(img_bgr: np.ndarray, model: str, target: int = 518):
+    """BGR uint8 [H, W, 3] photo -> (float32 [1, 3, h, w] blob, (src_h, src_w))
+    with (h, w) = native_size(model, H, W, target): the reference's
+    `preprocess_for(img_bgr, model, (target, .), stretch=False)` on the host."""
+    img = np.asarray(img_bgr)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"preprocess_native_host wants a uint8 [H, W, 3] BGR image, got {img.dtype} {img.shape}")
+    h, w = native_size(model, img.shape[0], img.shape[1], target)
+    x = img[:, :, ::-1].astype(SCALE_DTYPE[model]) / 255.0  # float32 stays float32 against a Python float
+    assert x.dtype == SCALE_DTYPE[model]
+    x = resize_cubic_float(x, h, w)
+    x = (x - np.asarray(IMAGENET_MEAN, np.float64)) / np.asarray(IMAGENET_STD, np.float64)  # float64
+    blob = np.ascontiguousarray(x.astype(np.float32).transpose(2, 0, 1)[None])
+    return blob, (img.shape[0], img.shape[1])
+
+
+def resize_cubic_f_norm(d_src: int, batch: int, sh: int, sw: int, pitch: int, swap_rb: bool, wide: bool, d_lut: int,
+                        mean, std, d_dst: int, oh: int, ow: int, stream: int = 0) -> None:
+    """Device pointers in/out, enqueued on `stream`: float32 NCHW out.  `d_lut`
+    is a device float[256] (wide false) or double[256] (wide true) holding
+    u / 255; mean and std are in output channel order."""
+    _lib.call("mde_op_resize_cubic_f_norm", C.c_void_p(int(d_src)), int(batch), int(sh), int(sw), int(pitch),
+              int(bool(swap_rb)), int(bool(wide)), C.c_void_p(int(d_lut)), *(float(m) for m in mean),
+              *(float(s) for s in std), C.c_void_p(int(d_dst)), int(oh), int(ow), C.c_void_p(int(stream or 0)))
+
+
+class NativePreprocess(_FramePreprocess):
+    """DevicePreprocess's counterpart for the native profile of
+    depth_anything_v2 / depth_anything_ac: owns the source frame (pinned host +
+    device) and the device table of u / 255 in the model's scale dtype; run /
+    run_device / fill_binding write the engine's "input" binding, float32
+    [batch][3][h][w] with (h, w) = `.dst` = native_size(model, src_h, src_w,
+    target), under the same stream-order rules.  The engine must have been
+    packed for that size."""
+
+    def __init__(self, src_h: int, src_w: int, model: str, target: int = 518, batch: int = 1):
+        self.model = model
+        self.target = int(target)
+        dst = native_size(model, src_h, src_w, target)
+        self.wide = SCALE_DTYPE[model] == np.float64
+        super().__init__((src_h, src_w), dst, batch, "float32_nchw", 4, scale_lut(model))
+
+    def _enqueue(self, d_src, pitch, swap_rb, d_dst, stream):
+        resize_cubic_f_norm(d_src, self.batch, self.src[0], self.src[1], pitch, swap_rb, self.wide, self.lut.device,
+                            IMAGENET_MEAN, IMAGENET_STD, d_dst, self.dst[0], self.dst[1], stream)
+
+
 __all__ = ["resize_linear_u8", "normalize_lut", "preprocess_host", "load_image_bgr", "resize_u8",
            "DevicePreprocess", "check_second_stage", "depth_pro_lut", "resize_bilinear_f32",
            "preprocess_depth_pro_host", "dp_preprocess", "DepthProPreprocess", "resize_cubic_u8",
            "square_pad_geometry", "box_window", "vggt_lut", "preprocess_vggt_host", "resize_cubic_u8_device",
-           "crop_f32", "VggtPreprocess"]
+           "crop_f32", "VggtPreprocess", "native_size", "scale_lut", "resize_cubic_float",
+           "preprocess_native_host", "resize_cubic_f_norm", "NativePreprocess"]
