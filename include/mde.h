@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define MDE_ABI_VERSION 11
+#define MDE_ABI_VERSION 12
 
 typedef enum {
   MDE_OK = 0,
@@ -342,6 +342,47 @@ int mde_op_linear_residual_split(const void* a_f16, int lda, const void* w_f16, 
                                  const float* bias, const float* layer_scale, float* x32, void* xh_f16, int ldx,
                                  float* ln_partials, int splitk, float* ws, size_t ws_floats, int* tile_cnt,
                                  int tile_cnt_cap, size_t slot_floats, void* stream);
+/* ---- since ABI 12: the row, head and patch-embed kernels that only the engine graphs reached, one thin
+ * test surface each (no reference counterpart; tests/test_gpu_rows.py, tests/test_gpu_engine_rows.py).
+ * No policy of their own. */
+/* mde_op_layernorm with fp32 output rows (the exact-fp32 engines' norm1 / norm2 and, with tokens and
+ * skip_cls, the taps' final norm: the cls row of every tokens-row sequence dropped, rows % tokens == 0). */
+int mde_op_layernorm32(const float* x, float* y, const float* gamma, const float* beta, int rows, int dim, float eps,
+                       int tokens, int skip_cls, void* stream);
+/* LayerNorm in place over rows [row0, tokens) of every sequence of x [nseq][tokens][dim]; rows [0, row0)
+ * are not touched (VGGT: DINOv2's final norm over the patch tokens).  dim: 128, 256, 384, 512, 768, 1024. */
+int mde_op_rows_layernorm(float* x, const float* gamma, const float* beta, int nseq, int tokens, int row0, int dim,
+                          float eps, void* stream);
+/* Rows [0, npre) of every sequence of x [nseq][tokens][dim] = pre [sets][npre][dim]: set 0 (sets == 1), or
+ * set 0 for sequence s with s % frames == 0 and set 1 for the others (sets == 2; VGGT's camera / register
+ * tokens).  dim % 4 == 0, x and pre 16-B aligned. */
+int mde_op_prefix_rows(float* x, const float* pre, int nseq, int tokens, int npre, int dim, int frames, int sets,
+                       void* stream);
+/* Row 0 of every sequence of x [nseq][tokens][dim] = cls [dim] (Depth Pro's cls + pos[0]). */
+int mde_op_cls_rows(float* x, const float* cls, int nseq, int tokens, int dim, void* stream);
+/* out[b] = bias + sum_k in[b][k] * w[k], fp32 accumulation (Depth Pro's fov head: the last conv over the
+ * whole map as a dot product). */
+int mde_op_fov_final(const void* in_f16, const float* w, float bias, int k, int batch, float* out, void* stream);
+/* out[m] = act(b2 + sum_c hid[m][c] * w2[c]) over fp32 hid [m][32] (16-B aligned): metric 0 ReLU, 1
+ * max_depth * sigmoid, 2 exp (the exact-fp32 head's last 1x1 conv; exp through the hardware's exp2). */
+int mde_op_head32(const float* hid, const float* w2, float b2, int m, int metric, float max_depth, float* out,
+                  void* stream);
+/* mde_op_patch_embed in the engines' form: the image's (h / 14) x (w / 14) whole patches (a remainder of
+ * rows / columns is cropped) to rows [tok0, tok0 + patches) of every tokens-row sequence of the fp32
+ * stream x32 or the f16 stream xh_f16 (exactly one of them).  cls_pos (optional, tok0 >= 1) -> row 0 of
+ * every sequence; without it rows [0, tok0) are not touched (a form of this test surface alone: the
+ * engines always pass a cls row, VGGT overwriting it with mde_op_prefix_rows' kernel).  With xh_f16: ln_partials (optional, dim % 32
+ * == 0) = fp32 [dim/32][batch*tokens][2], the folded-LayerNorm partials of the patch rows written, and of
+ * the cls rows copied from cls_st [dim/32][2]. */
+int mde_op_patch_embed_stream(const float* img, int batch, int h, int w, const void* w_f16, int ldw,
+                              const float* bias, const float* pos_patch, const float* cls_pos, int dim, int tokens,
+                              int tok0, void* patch_scratch_f16, float* x32, void* xh_f16, float* ln_partials,
+                              const float* cls_st, void* stream);
+/* The exact-fp32 engines' patch embed: fp32 patch rows [batch*patches][672] into patch_scratch_f32, fp32
+ * weights [dim_pad][ldw] (mde_op_linear32's layout), x32 [batch][patches + 1][dim]. */
+int mde_op_patch_embed32(const float* img, int batch, int h, int w, const float* w_f32, int ldw, const float* bias,
+                         const float* pos_patch, const float* cls_pos, int dim, float* patch_scratch_f32, float* x32,
+                         void* stream);
 /* uint8 NHWC image [batch][h][w][3] -> the patch-embed operand [batch*(h/14)*(w/14)][672] f16
  * (patch-major, channel, row, 16-wide padded column), computing ((float)u / scale - mean[c]) / std[c]
  * in fp32 (the ONNX preamble of reference core/onnx_tools.py:175-199: Cast, Div, Sub, Div). */
@@ -424,8 +465,8 @@ int mde_op_dp_preprocess(const unsigned char* src, int batch, int sh, int sw, in
                          const float* lut256, float* dst_f32_nchw, int oh, int ow, void* stream);
 int mde_op_dp_postprocess(const float* inv, int batch, int ih, int iw, const float* fov_deg, float f_px,
                           float* f_px_out, float* depth, int oh, int ow, void* stream);
-/* Point clouds (added to ABI 11 without a new version number -- purely additive, and
- * tests/test_depth_pro_photo_cpu.py pins mde_version() == 11; a caller that must know looks the symbol up):
+/* Point clouds (added to ABI 11 without a new version number -- purely additive; a caller that must
+ * know looks the symbol up):
  * the tail of reference models/depth_pro/onnx2trt_pointcloud.py (:172-184),
  * pinhole unprojection of metric depth into PLY binary_little_endian vertex records, on the device.
  * depth is fp32 [batch][h][w] (the output of mde_op_dp_postprocess / mde_op_depth_postprocess); photo is

@@ -159,6 +159,16 @@ PROTOTYPES = {
     "mde_op_linear_residual_split": [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p,
                                      c_int, c_size_t, c_void_p],
+    "mde_op_layernorm32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_void_p],
+    "mde_op_rows_layernorm": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p],
+    "mde_op_prefix_rows": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "mde_op_cls_rows": [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    "mde_op_fov_final": [c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p],
+    "mde_op_head32": [c_void_p, c_void_p, c_float, c_int, c_int, c_float, c_void_p, c_void_p],
+    "mde_op_patch_embed_stream": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "mde_op_patch_embed32": [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                             c_void_p, c_void_p, c_void_p],
     "mde_op_patch_prep_u8": [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "mde_op_dp_pyramid_patches": [c_void_p, c_int, c_int, c_void_p, c_void_p],
     "mde_op_merge_tokens": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float,

@@ -176,13 +176,15 @@ __global__ void __launch_bounds__(256) patch_prep_kernel(const float* __restrict
     return;
   }
   id -= nchunk;
-  if (id < (long long)B * D) {
+  // the cls row of every sequence (neither X nor Xh: no row is written -- a
+  // stream whose first rows another kernel fills)
+  if ((X || Xh) && id < (long long)B * D) {
     const int b = (int)(id / D), d = (int)(id - (long long)(id / D) * D);
     if (Xh) Xh[(size_t)b * T * D + d] = (f16)cls_pos[d];
     else X[(size_t)b * T * D + d] = cls_pos[d];
     return;
   }
-  id -= (long long)B * D;
+  if (X || Xh) id -= (long long)B * D;
   // the cls rows' LayerNorm partials (folded LN, GemmParams::lnst_out): the
   // row is the same f16 vector in every image, its partials come packed
   if (lnst && id < (long long)B * (D / 16)) {
@@ -367,9 +369,11 @@ hipError_t launch_layernorm32(const float* x, float* y, const float* g, const fl
 
 hipError_t launch_patch_prep(const float* img, h16* P, float* X, const float* cls_pos, int B, int H, int W, int ph,
                              int pw, int T, int D, hipStream_t st, h16* Xh, float* lnst, const float* cls_st, float* P32) {
-  if (lnst && (!cls_st || (D & 31))) return hipErrorInvalidValue;
+  if (lnst && (!cls_st || (D & 31) || !(X || Xh))) return hipErrorInvalidValue;
+  if ((X || Xh) && !cls_pos) return hipErrorInvalidValue;
   if (H < ph * 14 || W < pw * 14) return hipErrorInvalidValue;
-  const long long n = (long long)B * 3 * ph * 14 * pw + (long long)B * D + (lnst ? (long long)B * (D / 16) : 0);
+  const long long n = (long long)B * 3 * ph * 14 * pw + ((X || Xh) ? (long long)B * D : 0) +
+                      (lnst ? (long long)B * (D / 16) : 0);
   if (n <= 0) return hipSuccess;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   if (P32)

@@ -41,11 +41,24 @@ MDE_DEV float wave_sum(float v) {
   return v;
 }
 
+// A row's mean, sum * (1 / D) rounded to fp32 before it is used.  Left to the
+// compiler, x - sum * invd contracts into fma(-sum, invd, x): the deviation is
+// then taken from the unrounded product, and a row of equal values c whose
+// mean rounds to c (D = 384, 768: 1 / D is not a power of two) gets deviations
+// of c 2^-25 instead of 0, which rstd = eps^-1/2 = 1000 turns into 5e-5 at
+// c = 1.5 (tests/test_gpu_rows.py, the const family).
+// (__fmul_rn is a plain product to this compiler; the pragma is what keeps it apart.)
+MDE_DEV float row_mean(float sum, float invd) {
+#pragma clang fp contract(off)
+  return sum * invd;
+}
+
 // LayerNorm of one row of D = 64 PER fp32 values by one wave: lane `lane`
 // holds columns i * 64 + lane in v[i] and hands column c's result to
 // store(c, value).  Two passes (mean, then the squared deviations), sums in
 // index order then wave_sum: every kernel that calls this gives the same bits
-// for the same row.  Compiled with the caller's contraction setting.
+// for the same row.  Compiled with the caller's contraction setting, except
+// the mean: it is rounded once (row_mean), then subtracted.
 template <int PER, class Store>
 MDE_DEV void row_layernorm(const float (&v)[PER], int lane, const float* __restrict__ g,
                            const float* __restrict__ bt, float eps, Store&& store) {
@@ -53,7 +66,7 @@ MDE_DEV void row_layernorm(const float (&v)[PER], int lane, const float* __restr
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < PER; ++i) s += v[i];
-  const float mean = wave_sum(s) * (1.0f / D);
+  const float mean = row_mean(wave_sum(s), 1.0f / D);
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < PER; ++i) {

@@ -946,4 +946,130 @@ int mde_op_linear_residual_split(const void* a, int lda, const void* wt, int ldw
   OP_RET(launch_gemm(g, (hipStream_t)st), "linear_residual_split");
 }
 
+// ---- ABI 12: the row / head / patch-embed kernels only the engine graphs reached, one wrapper each ----
+// (no kernel code and no policy here; tests/test_gpu_rows.py, tests/test_gpu_engine_rows.py)
+namespace {
+// a [nseq][tokens][dim] stream addressed by a kernel with one thread per element or per row
+const char* stream_rows_error(int nseq, int tokens, int dim) {
+  if (nseq < 1 || tokens < 1 || dim < 1) return "nseq, tokens and dim must be positive";
+  if ((long long)nseq * tokens >= 0x7fffffffLL / 4) return "nseq * tokens of 2^29 or more";
+  return nullptr;
+}
+}  // namespace
+
+int mde_op_layernorm32(const float* x, float* y, const float* g, const float* b, int rows, int dim, float eps,
+                       int tokens, int skip_cls, void* st) {
+  if (!x || !y || !g || !b) return fail(MDE_ERR_ARG, "mde_op_layernorm32: null argument");
+  if (rows < 0) return fail(MDE_ERR_ARG, "mde_op_layernorm32: negative rows");
+  if (skip_cls && tokens < 2) return fail(MDE_ERR_ARG, "mde_op_layernorm32: skip_cls needs tokens >= 2");
+  if (skip_cls && rows % tokens) return fail(MDE_ERR_ARG, "mde_op_layernorm32: skip_cls needs rows % tokens == 0");
+  OP_RET(launch_layernorm32(x, y, g, b, rows, dim, eps, (hipStream_t)st, tokens > 0 ? tokens : 1, skip_cls),
+         "mde_op_layernorm32");
+}
+
+int mde_op_rows_layernorm(float* x, const float* g, const float* b, int nseq, int tokens, int row0, int dim, float eps,
+                          void* st) {
+  const char* why = (!x || !g || !b) ? "null argument" : stream_rows_error(nseq, tokens, dim);
+  if (!why && (row0 < 0 || row0 >= tokens)) why = "row0 outside [0, tokens)";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_rows_layernorm: ") + why);
+  OP_RET(launch_rows_layernorm(x, g, b, nseq, tokens, row0, dim, eps, (hipStream_t)st), "mde_op_rows_layernorm");
+}
+
+int mde_op_prefix_rows(float* x, const float* pre, int nseq, int tokens, int npre, int dim, int frames, int sets,
+                       void* st) {
+  const char* why = (!x || !pre) ? "null argument" : stream_rows_error(nseq, tokens, dim);
+  if (!why && (npre < 1 || npre > tokens)) why = "npre outside [1, tokens]";
+  if (!why && (dim & 3)) why = "dim % 4 != 0";
+  if (!why && sets != 1 && sets != 2) why = "sets must be 1 or 2";
+  if (!why && frames < 1) why = "frames must be positive";
+  if (!why && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(pre)) & 15))
+    why = "x and pre must be 16-byte aligned";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_prefix_rows: ") + why);
+  OP_RET(launch_prefix_rows(x, pre, nseq, tokens, npre, dim, frames, sets, (hipStream_t)st), "mde_op_prefix_rows");
+}
+
+int mde_op_cls_rows(float* x, const float* cls, int nseq, int tokens, int dim, void* st) {
+  const char* why = (!x || !cls) ? "null argument" : stream_rows_error(nseq, tokens, dim);
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_cls_rows: ") + why);
+  OP_RET(launch_cls_rows(x, cls, nseq, tokens, dim, (hipStream_t)st), "mde_op_cls_rows");
+}
+
+int mde_op_fov_final(const void* in_f16, const float* w, float bias, int k, int batch, float* out, void* st) {
+  if (!in_f16 || !w || !out) return fail(MDE_ERR_ARG, "mde_op_fov_final: null argument");
+  if (k < 1 || batch < 1) return fail(MDE_ERR_ARG, "mde_op_fov_final: k and batch must be positive");
+  OP_RET(launch_fov_final((const h16*)in_f16, w, bias, k, batch, out, (hipStream_t)st), "mde_op_fov_final");
+}
+
+int mde_op_head32(const float* hid, const float* w2, float b2, int m, int metric, float max_depth, float* out,
+                  void* st) {
+  if (!hid || !w2 || !out) return fail(MDE_ERR_ARG, "mde_op_head32: null argument");
+  if (m < 1) return fail(MDE_ERR_ARG, "mde_op_head32: m must be positive");
+  if (metric < 0 || metric > 2) return fail(MDE_ERR_ARG, "mde_op_head32: metric must be 0 (ReLU), 1 (sigmoid) or 2 (exp)");
+  if (reinterpret_cast<uintptr_t>(hid) & 15) return fail(MDE_ERR_ARG, "mde_op_head32: hid must be 16-byte aligned");
+  OP_RET(launch_head32(hid, w2, b2, m, metric, max_depth, out, (hipStream_t)st), "mde_op_head32");
+}
+
+int mde_op_patch_embed_stream(const float* img, int batch, int h, int w, const void* wt, int ldw, const float* bias,
+                              const float* pos_patch, const float* cls_pos, int dim, int tokens, int tok0,
+                              void* scratch, float* x32, void* xh, float* ln_partials, const float* cls_st,
+                              void* st) {
+  const char* why = nullptr;
+  const int ph = h / 14, pw = w / 14;
+  if (!img || !wt || !bias || !pos_patch || !scratch) why = "null argument";
+  else if (!x32 == !xh) why = "exactly one of x32 / xh_f16";
+  else if (batch < 1 || ph < 1 || pw < 1 || dim < 1) why = "batch and dim positive, h and w at least 14";
+  else if (tok0 < 0 || (long long)tok0 + (long long)ph * pw > tokens) why = "tok0 + patches exceeds tokens";
+  else if (cls_pos && tok0 < 1) why = "a cls row needs tok0 >= 1";
+  else if ((ln_partials || cls_st) && !(xh && ln_partials && cls_st && cls_pos))
+    why = "ln_partials and cls_st come together, with xh_f16 and cls_pos";
+  else if (ln_partials && (dim & 31)) why = "ln_partials need dim % 32 == 0";
+  if (why) return fail(MDE_ERR_ARG, std::string("mde_op_patch_embed_stream: ") + why);
+  // cls_pos null: no cls row (rows [0, tok0) of every sequence belong to another kernel)
+  hipError_t e = launch_patch_prep(img, (h16*)scratch, cls_pos ? x32 : nullptr, cls_pos, batch, h, w, ph, pw, tokens,
+                                   dim, (hipStream_t)st, cls_pos ? (h16*)xh : nullptr, ln_partials, cls_st);
+  if (e != hipSuccess) return op_status(e, "mde_op_patch_embed_stream (patch_prep)");
+  GemmParams g = gemm_dense((const h16*)scratch, 672, (const h16*)wt, ldw, batch * ph * pw, dim, 672);
+  g.emode = E_PATCH;
+  g.bias = bias;
+  g.x32 = x32;
+  g.xh = (h16*)xh;
+  g.ldo = dim;
+  g.T = tokens;
+  g.tok0 = tok0;
+  g.pos = pos_patch;
+  g.npatch = ph * pw;
+  if (ln_partials) set_ln_producer(g, ln_partials, batch * tokens);
+  OP_RET(launch_gemm(g, (hipStream_t)st), "mde_op_patch_embed_stream");
+}
+
+int mde_op_patch_embed32(const float* img, int batch, int h, int w, const float* wt, int ldw, const float* bias,
+                         const float* pos_patch, const float* cls_pos, int dim, float* scratch32, float* x32,
+                         void* st) {
+  const int ph = h / 14, pw = w / 14;
+  if (!img || !wt || !bias || !pos_patch || !cls_pos || !scratch32 || !x32)
+    return fail(MDE_ERR_ARG, "mde_op_patch_embed32: null argument");
+  if (batch < 1 || ph < 1 || pw < 1 || dim < 1)
+    return fail(MDE_ERR_ARG, "mde_op_patch_embed32: batch and dim positive, h and w at least 14");
+  const int T = ph * pw + 1;
+  hipError_t e = launch_patch_prep(img, nullptr, x32, cls_pos, batch, h, w, ph, pw, T, dim, (hipStream_t)st, nullptr,
+                                   nullptr, nullptr, scratch32);
+  if (e != hipSuccess) return op_status(e, "mde_op_patch_embed32 (patch_prep)");
+  Gemm32Params g;
+  g.emode = E_PATCH;
+  g.A = scratch32;
+  g.lda = 672;
+  g.W = wt;
+  g.ldw = ldw;
+  g.M = batch * ph * pw;
+  g.N = dim;
+  g.K = 672;
+  g.bias = bias;
+  g.x32 = x32;
+  g.ldo = dim;
+  g.T = T;
+  g.pos = pos_patch;
+  g.npatch = ph * pw;
+  OP_RET(launch_gemm32(g, (hipStream_t)st), "mde_op_patch_embed32");
+}
+
 }  // extern "C"

@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) tap_concat_ln_kernel(const float* __restr
     vb[i] = xb[src + i * 64 + lane];
     s += va[i] + vb[i];
   }
-  const float mean = wave_sum(s) * (1.0f / (2 * D));
+  const float mean = row_mean(wave_sum(s), 1.0f / (2 * D));
   float qv = 0.f;
 #pragma unroll
   for (int i = 0; i < PER; ++i) {

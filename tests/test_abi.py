@@ -221,3 +221,47 @@ def test_engine_path_wrappers_reject_bad_arguments(lib_path):
         b"max(splitk, 4)")
     err(rs(p, 1536, p, 1536, 300, 384, 1536, p, p, p, None, 384, None, 4, p, 1 << 22, p, 29, 1 << 22, None),
         b"fewer counters")
+
+
+def test_row_and_head_wrappers_reject_bad_arguments(lib_path):
+    """The ABI 12 wrappers (mde_op_layernorm32 ... mde_op_patch_embed32) answer null pointers and sizes
+    their kernels cannot take before any launch (the pointers below are never dereferenced)."""
+    from monocular_depth_estimation_trt_amd import _lib
+    L = _lib.lib()
+    p = 4096
+
+    def err(rc, msg):
+        assert rc == 1, (rc, L.mde_last_error())
+        assert msg in L.mde_last_error(), L.mde_last_error()
+
+    err(L.mde_op_layernorm32(p, None, p, p, 21, 384, 1e-6, 7, 0, None), b"mde_op_layernorm32: null")
+    err(L.mde_op_layernorm32(p, p, p, p, 21, 384, 1e-6, 1, 1, None), b"tokens >= 2")
+    err(L.mde_op_layernorm32(p, p, p, p, 20, 384, 1e-6, 7, 1, None), b"rows % tokens")
+    err(L.mde_op_layernorm32(p, p, p, p, 21, 512, 1e-6, 7, 0, None), b"invalid shape")      # not a layernorm width
+    err(L.mde_op_rows_layernorm(None, p, p, 3, 9, 5, 384, 1e-5, None), b"mde_op_rows_layernorm: null")
+    err(L.mde_op_rows_layernorm(p, p, p, 3, 9, 9, 384, 1e-5, None), b"row0 outside")
+    err(L.mde_op_rows_layernorm(p, p, p, 3, 9, 5, 320, 1e-5, None), b"invalid shape")
+    err(L.mde_op_prefix_rows(p, None, 6, 9, 5, 384, 3, 2, None), b"mde_op_prefix_rows: null")
+    err(L.mde_op_prefix_rows(p, p, 6, 9, 10, 384, 3, 2, None), b"npre outside")
+    err(L.mde_op_prefix_rows(p, p, 6, 9, 5, 382, 3, 2, None), b"dim % 4")
+    err(L.mde_op_prefix_rows(p, p, 6, 9, 5, 384, 3, 3, None), b"sets must be")
+    err(L.mde_op_prefix_rows(p, p, 6, 9, 5, 384, 0, 2, None), b"frames")
+    err(L.mde_op_prefix_rows(p + 4, p, 6, 9, 5, 384, 3, 2, None), b"16-byte")
+    err(L.mde_op_cls_rows(p, None, 3, 7, 384, None), b"mde_op_cls_rows: null")
+    err(L.mde_op_cls_rows(p, p, 0, 7, 384, None), b"must be positive")
+    err(L.mde_op_fov_final(None, p, 0.5, 1000, 3, p, None), b"mde_op_fov_final: null")
+    err(L.mde_op_fov_final(p, p, 0.5, 0, 3, p, None), b"must be positive")
+    err(L.mde_op_head32(p, None, 0.1, 300, 1, 20.0, p, None), b"mde_op_head32: null")
+    err(L.mde_op_head32(p, p, 0.1, 300, 3, 20.0, p, None), b"metric must be")
+    err(L.mde_op_head32(p + 4, p, 0.1, 300, 1, 20.0, p, None), b"16-byte")
+    pes = L.mde_op_patch_embed_stream
+    err(pes(p, 2, 98, 98, p, 704, p, p, p, 384, 50, 1, None, p, None, None, None, None), b"null")
+    err(pes(p, 2, 98, 98, p, 704, p, p, p, 384, 50, 1, p, p, p, None, None, None), b"exactly one of")
+    err(pes(p, 2, 98, 98, p, 704, p, p, p, 384, 49, 1, p, p, None, None, None, None), b"exceeds tokens")
+    err(pes(p, 2, 98, 13, p, 704, p, p, p, 384, 50, 1, p, p, None, None, None, None), b"at least 14")
+    err(pes(p, 2, 98, 98, p, 704, p, p, p, 384, 49, 0, p, p, None, None, None, None), b"tok0 >= 1")
+    err(pes(p, 2, 98, 98, p, 704, p, p, p, 384, 50, 1, p, p, None, p, p, None), b"come together")     # partials need xh
+    err(pes(p, 2, 98, 98, p, 704, p, p, None, 384, 54, 5, p, None, p, p, p, None), b"come together")  # and a cls row
+    err(pes(p, 2, 98, 98, p, 704, p, p, p, 400, 50, 1, p, None, p, p, p, None), b"dim % 32")
+    err(L.mde_op_patch_embed32(p, 2, 98, 98, p, 672, p, p, None, 384, p, p, None), b"mde_op_patch_embed32: null")
+    err(L.mde_op_patch_embed32(p, 0, 98, 98, p, 672, p, p, p, 384, p, p, None), b"positive")

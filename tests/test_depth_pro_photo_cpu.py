@@ -218,5 +218,5 @@ def test_dp_postprocess_checks_arguments_before_any_device_call(lib, kw):
     assert b"mde_op_dp_postprocess:" in lib.mde_last_error(), (kw, lib.mde_last_error())
 
 
-def test_abi_version_is_11(lib):
-    assert lib.mde_version() == 11
+def test_abi_version_is_12(lib):
+    assert lib.mde_version() == 12

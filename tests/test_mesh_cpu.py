@@ -278,7 +278,7 @@ WS88 = 2 * 4 + 8 * 8 * 5   # mde_op_depth_mesh_ws_bytes(1, 8, 8, 1)
 def test_prototypes_and_ws_bytes(lib):
     assert "mde_op_depth_mesh" in _lib.PROTOTYPES and "mde_op_depth_mesh_ws_bytes" in _lib.PROTOTYPES
     assert len(_lib.PROTOTYPES["mde_op_depth_mesh"]) == 27
-    assert lib.mde_version() == 11
+    assert lib.mde_version() == 12
     f = lib.mde_op_depth_mesh_ws_bytes
     # two ints per tile of 1024 samples, an int32 index and a flag byte per sample
     assert f(1, 8, 8, 1) == WS88 == pc.mesh_ws_bytes(1, 8, 8)
