@@ -131,8 +131,14 @@ int mde_tuning_get(const char* name, int* value);
  * slices=1 fused=0 resize_first=0".  kind: none (nothing launched yet, or an
  * empty problem), tile, split_store, split_resid (these three with every
  * field: block tile, wave grid, K-step, LDS ring depth, split-K slices, fused
- * split tail, a resize launch in front), conv_direct (resize_first only),
- * panel, gemm256.  MDE_ERR_ARG: null buffer, or n too small (128 suffices). */
+ * split tail, a resize launch in front), conv_direct ("kind=conv_direct
+ * conv=upconv resize_first=0": conv names the kernel of conv.hip that ran --
+ * conv3 the per-tile direct conv, conv3_up the same kernel with its four-tap
+ * upsampling loader, upconv / upconv_persist the separable upsampling conv
+ * with one tile per workgroup / on its persistent grid, conv64p the
+ * persistent 64-channel conv -- and resize_first), panel, gemm256.  A reader
+ * takes the fields by name: later versions may add some.  MDE_ERR_ARG: null
+ * buffer, or n too small (128 suffices). */
 int mde_debug_last_gemm_route(char* buf, size_t n);
 
 /* ---- engine (replaces get_engine / ICudaEngine) ----------------------- */

@@ -346,11 +346,12 @@ def tuning(**switches):
 
 def last_gemm_route() -> dict:
     """The route this thread's last GEMM-family launch took (include/mde.h
-    mde_debug_last_gemm_route): {"kind": "tile", "bm": 128, ...}."""
+    mde_debug_last_gemm_route): {"kind": "tile", "bm": 128, ...}, or
+    {"kind": "conv_direct", "conv": "upconv", "resize_first": 0}."""
     buf = C.create_string_buffer(256)
     call("mde_debug_last_gemm_route", buf, len(buf))
     fields = dict(f.split("=", 1) for f in buf.value.decode().split())
-    return {k: v if k == "kind" else int(v) for k, v in fields.items()}
+    return {k: v if k in ("kind", "conv") else int(v) for k, v in fields.items()}
 
 
 def exported_symbols():

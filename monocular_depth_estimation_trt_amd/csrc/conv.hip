@@ -1248,25 +1248,38 @@ int upconv_grid() {
   const int per_cu = 163840 / lds < 4 ? 163840 / lds : 4;
   return 256 * (per_cu > 0 ? per_cu : 1);
 }
+// tiles of p and the persistent grid of its channel count (0: no such kernel)
+long long upconv_tiles(const GemmParams& p) {
+  return (long long)p.cb * ((p.oh + UTH - 1) / UTH) * ((p.ow + UTW - 1) / UTW);
+}
+int upconv_grid_of(const GemmParams& p) {
+  switch (p.cc / 32) {
+    case 1: return upconv_grid<1>();
+    case 2: return upconv_grid<2>();
+    case 3: return upconv_grid<3>();
+    case 4: return upconv_grid<4>();
+    default: return 0;
+  }
+}
 template <int NCH, int EM>
-void launch_upconv_n(const GemmParams& p, long long tiles, hipStream_t st) {
+void launch_upconv_n(const GemmParams& p, long long tiles, bool persist, hipStream_t st) {
   const int grid = upconv_grid<NCH>();
-  if (tiles > grid)
+  if (persist)
     hipLaunchKernelGGL((upconv_kernel<NCH, EM, true>), dim3((unsigned)grid), dim3(512), 0, st, p);
   else
     hipLaunchKernelGGL((upconv_kernel<NCH, EM, false>), dim3((unsigned)tiles), dim3(512), 0, st, p);
 }
 
 template <int EM>
-hipError_t launch_upconv(const GemmParams& p, hipStream_t st) {
-  const long long tiles = (long long)p.cb * ((p.oh + UTH - 1) / UTH) * ((p.ow + UTW - 1) / UTW);
+hipError_t launch_upconv(const GemmParams& p, bool persist, hipStream_t st) {
+  const long long tiles = upconv_tiles(p);
   if (tiles <= 0) return hipSuccess;
   if (tiles >= (1ll << 31)) return hipErrorInvalidValue;
   switch (p.cc / 32) {
-    case 1: launch_upconv_n<1, EM>(p, tiles, st); break;
-    case 2: launch_upconv_n<2, EM>(p, tiles, st); break;
-    case 3: launch_upconv_n<3, EM>(p, tiles, st); break;
-    case 4: launch_upconv_n<4, EM>(p, tiles, st); break;
+    case 1: launch_upconv_n<1, EM>(p, tiles, persist, st); break;
+    case 2: launch_upconv_n<2, EM>(p, tiles, persist, st); break;
+    case 3: launch_upconv_n<3, EM>(p, tiles, persist, st); break;
+    case 4: launch_upconv_n<4, EM>(p, tiles, persist, st); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -1297,11 +1310,28 @@ bool conv3_takes_res1_up(const GemmParams& p) {
          p.res1_uw > 0;
 }
 
+// The one place that picks launch_conv3's kernel (host policy, no device
+// call); gemm_route() records the answer, launch_conv3 launches from it.
+int conv3_kernel_choice(const GemmParams& p) {
+  if (p.amode == A_CONV3_UP) {
+    if (!upconv_eligible(p)) return CONV_K_CONV3_UP;
+    // more tiles than the persistent grid holds: its workgroups walk them
+    return upconv_tiles(p) > upconv_grid_of(p) ? CONV_K_UPCONV_PERSIST : CONV_K_UPCONV;
+  }
+  // (a folded 1x1 exists in the persistent conv only: conv64p_launch checks it)
+  if (p.emode == E_STORE && (p.pw_w || conv64p_mode(p) >= 0)) return CONV_K_CONV64P;
+  return CONV_K_CONV3;
+}
+
 hipError_t launch_conv3(const GemmParams& p, hipStream_t st) {
   if (p.M <= 0 || p.N <= 0) return hipSuccess;
   if (!conv_direct_supported(p) || (p.N & 7) || (p.ldw & 63) || p.ldw < 9 * p.cc) return hipErrorInvalidValue;
   const bool up = p.amode == A_CONV3_UP;
-  if (up && upconv_eligible(p)) return p.emode == E_HEAD ? launch_upconv<E_HEAD>(p, st) : launch_upconv<E_STORE>(p, st);
+  const int kernel = conv3_kernel_choice(p);
+  if (kernel == CONV_K_UPCONV || kernel == CONV_K_UPCONV_PERSIST) {
+    const bool persist = kernel == CONV_K_UPCONV_PERSIST;
+    return p.emode == E_HEAD ? launch_upconv<E_HEAD>(p, persist, st) : launch_upconv<E_STORE>(p, persist, st);
+  }
   const bool ck64 = (p.cc % 64) == 0 && p.stride == 1;
   if (p.emode == E_HEAD) {
     if (p.N != 32 || p.stride != 1) return hipErrorInvalidValue;
@@ -1310,7 +1340,7 @@ hipError_t launch_conv3(const GemmParams& p, hipStream_t st) {
   }
   if (p.emode != E_STORE) return hipErrorInvalidValue;
   hipError_t err;
-  if (!up && conv64p_launch(p, st, err)) return err;
+  if (kernel == CONV_K_CONV64P && conv64p_launch(p, st, err)) return err;
   if (up) return ck64 ? conv_tiles<64, 1, true, E_STORE>(p, st) : conv_tiles<32, 1, true, E_STORE>(p, st);
   if (p.stride == 2) return conv_tiles<32, 2, false, E_STORE>(p, st);
   return ck64 ? conv_tiles<64, 1, false, E_STORE>(p, st) : conv_tiles<32, 1, false, E_STORE>(p, st);

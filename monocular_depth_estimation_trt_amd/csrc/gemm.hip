@@ -775,6 +775,13 @@ GemmRoute split_resid_route(const GemmParams& p) {
   return tile_route(ROUTE_SPLIT_RESID, t, S, fused_split(p, big ? t128 : t64, S, kTiles[t].bm, kTiles[t].bn));
 }
 
+// the direct-conv route of p: conv.hip's choice of kernel recorded with it
+GemmRoute conv_route(const GemmParams& p) {
+  GemmRoute r{ROUTE_CONV_DIRECT};
+  r.conv = conv3_kernel_choice(p);
+  return r;
+}
+
 thread_local GemmRoute t_last_route;
 
 }  // namespace
@@ -797,7 +804,7 @@ hipError_t gemm_route(const GemmParams& p, GemmRoute& r) {
     // epilogue, or written into res1 first for every other route
     if (!p.res1 || p.amode != A_CONV3 || p.emode != E_STORE || p.res1_uh <= 0 || p.res1_uw <= 0 || (p.N & 7))
       return hipErrorInvalidValue;
-    if (store_split_slices(p) <= 1 && !prefer_im2col(p) && conv3_takes_res1_up(p)) return take({ROUTE_CONV_DIRECT});
+    if (store_split_slices(p) <= 1 && !prefer_im2col(p) && conv3_takes_res1_up(p)) return take(conv_route(p));
     GemmParams q = p;
     q.res1_up = nullptr;
     const hipError_t e = gemm_route(q, r);
@@ -822,7 +829,7 @@ hipError_t gemm_route(const GemmParams& p, GemmRoute& r) {
     const long long t64 = tiles(p.M, p.N, 64, 64);
     return take(tile_route(ROUTE_SPLIT_STORE, deep64(t64 * S) ? T64_DEEP : T64, S, fused_split(p, t64, S, 64, 64)));
   }
-  if (p.amode != A_DENSE && conv_direct_supported(p) && !prefer_im2col(p)) return take({ROUTE_CONV_DIRECT});
+  if (p.amode != A_DENSE && conv_direct_supported(p) && !prefer_im2col(p)) return take(conv_route(p));
   if ((p.emode == E_RESID || p.emode == E_PATCH) && p.xh && ((uintptr_t)p.xh & 15)) return hipErrorInvalidValue;
   if (p.emode == E_RESID && p.splitk > 1 && p.partial && p.amode == A_DENSE && !narrow_resid(p))
     return take(split_resid_route(p));

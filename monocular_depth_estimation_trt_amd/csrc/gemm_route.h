@@ -14,7 +14,7 @@ enum GemmRouteKind : int {
   ROUTE_TILE,          // one gemm_kernel launch (gemm.hip)
   ROUTE_SPLIT_STORE,   // E_STORE split-K: `slices` K slices of gemm_kernel on 64^2 tiles
   ROUTE_SPLIT_RESID,   // E_RESID split-K: `slices` K slices on 64^2 or 128^2 tiles
-  ROUTE_CONV_DIRECT,   // launch_conv3 (conv.hip picks its kernel)
+  ROUTE_CONV_DIRECT,   // launch_conv3 on the kernel `conv` names (conv.hip: conv3_kernel_choice)
   ROUTE_PANEL,         // launch_panel_gemm (gemm_panel.hip)
   ROUTE_GEMM256        // launch_gemm256 (gemm256.hip)
 };
@@ -28,6 +28,7 @@ struct GemmRoute {
   int fused = 0;         // SPLIT_*: the split tail fused into the slices' launch (GemmParams::tile_cnt);
                          // 0: slices into the workspace, then the reduce launch
   int resize_first = 0;  // res1_up written into res1 by a resize launch before this route
+  int conv = 0;          // CONV_DIRECT: the ConvKernel (mde_ops.h) launch_conv3 launches
 };
 
 // Validates p as launch_gemm always has and picks its route.  hipSuccess with

@@ -172,6 +172,17 @@ bool conv_direct_supported(const GemmParams& p);
 // the direct conv takes p's res1 through GemmParams::res1_up (conv.hip)
 bool conv3_takes_res1_up(const GemmParams& p);
 hipError_t launch_conv3(const GemmParams& p, hipStream_t st);
+// the kernel launch_conv3 launches for p (conv.hip; policy only, no device
+// call): launch_conv3 acts on it and gemm_route records it (GemmRoute::conv)
+enum ConvKernel : int {
+  CONV_K_NONE = 0,        // not a direct-conv route
+  CONV_K_CONV3,           // conv3_kernel on the map itself
+  CONV_K_CONV3_UP,        // conv3_kernel, four-tap upsampling loader (A_CONV3_UP)
+  CONV_K_UPCONV,          // upconv_kernel, one tile per workgroup
+  CONV_K_UPCONV_PERSIST,  // upconv_kernel, persistent grid
+  CONV_K_CONV64P          // the persistent 64-channel conv
+};
+int conv3_kernel_choice(const GemmParams& p);
 // the persistent 64-channel conv (conv.hip) takes p and would run a following
 // 1x1 (GemmParams::pw_*) on its tiles
 bool conv64p_folds_pointwise(const GemmParams& p);

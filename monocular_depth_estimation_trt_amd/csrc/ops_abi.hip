@@ -26,6 +26,7 @@ static int op_status(hipError_t e, const char* what) {
 
 int mde_debug_last_gemm_route(char* buf, size_t n) {
   static const char* const kKind[] = {"none", "tile", "split_store", "split_resid", "conv_direct", "panel", "gemm256"};
+  static const char* const kConv[] = {"none", "conv3", "conv3_up", "upconv", "upconv_persist", "conv64p"};
   const GemmRoute& r = gemm_last_route();
   if (!buf) return fail(MDE_ERR_ARG, "mde_debug_last_gemm_route: null buffer");
   int len;
@@ -33,7 +34,8 @@ int mde_debug_last_gemm_route(char* buf, size_t n) {
     len = snprintf(buf, n, "kind=%s bm=%d bn=%d wm=%d wn=%d bk=%d stages=%d slices=%d fused=%d resize_first=%d",
                    kKind[r.kind], r.bm, r.bn, r.wm, r.wn, r.bk, r.stages, r.slices, r.fused, r.resize_first);
   else if (r.kind == ROUTE_CONV_DIRECT)
-    len = snprintf(buf, n, "kind=%s resize_first=%d", kKind[r.kind], r.resize_first);
+    len = snprintf(buf, n, "kind=%s conv=%s resize_first=%d", kKind[r.kind],
+                   kConv[r.conv >= 0 && r.conv <= CONV_K_CONV64P ? r.conv : 0], r.resize_first);
   else
     len = snprintf(buf, n, "kind=%s", kKind[r.kind >= 0 && r.kind <= ROUTE_GEMM256 ? r.kind : 0]);
   if (len < 0 || (size_t)len >= n) return fail(MDE_ERR_ARG, "mde_debug_last_gemm_route: buffer too small");

@@ -283,6 +283,7 @@ GELU_SITES = [
 GELU_TABLE_SHAPE = (7936, 64, 8)    # the 64^2-tile site: every (value, class) pair exactly once
 GELU32_SHAPE = (1588, 96, 40)       # mde_op_linear32 (erff)
 GELU_CONV = (1, 31, 32, 64)         # B, h, w, channels: 31 x 32 x 64 = NSEQ
+GELU_UPCONV = (8, 8, 31, 32)        # conv3x3_up at ratio 1: 8 rows, a map upconv_kernel takes (<= 12 source rows)
 
 
 def gelu64(x):

@@ -91,3 +91,44 @@ def depth_metrics(got: np.ndarray, ref: np.ndarray) -> dict:
     return dict(max_abs=float(d.max()), mean_abs=float(d.mean()),
                 rel_mean=float(d.mean() / max(np.abs(r).mean(), 1e-12)),
                 corr=float(np.corrcoef(g, r)[0, 1]) if g.size > 1 else 1.0)
+
+
+# ---- exact comparisons and the route record (test_gpu_exact.py, test_gpu_bilinear.py) ----
+
+def ordinal16(t):
+    """f16 -> int32, monotone in the value (+0 and -0 both 0): differences are ulps."""
+    b = t.contiguous().view(torch.int16).int()
+    return torch.where(b < 0, -(b & 0x7FFF), b)
+
+
+def assert_equal(got, ref, what):
+    """torch.equal(got, ref) by value (zeros of either sign agree, NaN never
+    does); on failure the count, the bounding box and the largest difference."""
+    g = got.detach().cpu()
+    assert g.shape == ref.shape and g.dtype == ref.dtype, (what, g.shape, ref.shape, g.dtype, ref.dtype)
+    if torch.equal(g, ref):
+        return
+    g2, r2 = g.reshape(-1, g.shape[-1]), ref.reshape(-1, ref.shape[-1])
+    bad = g2 != r2
+    rows, cols = bad.any(1).nonzero().flatten(), bad.any(0).nonzero().flatten()
+    if g.dtype == torch.float16:
+        d = (ordinal16(g2) - ordinal16(r2)).abs()[bad]
+        worst = f"max {int(d.max())} f16 ulp"
+    else:
+        worst = f"max |d| {float((g2.double() - r2.double()).abs()[bad].nan_to_num(float('inf')).max()):.3e}"
+    i = int(bad.flatten().nonzero()[0])
+    raise AssertionError(
+        f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from float64, rows {int(rows[0])}..{int(rows[-1])} "
+        f"cols {int(cols[0])}..{int(cols[-1])} of {tuple(g2.shape)}, {worst}, {int(torch.isnan(g2).sum())} NaN; "
+        f"first [{i // g2.shape[1]}][{i % g2.shape[1]}] got {float(g2.flatten()[i])!r} ref {float(r2.flatten()[i])!r}")
+
+
+def assert_route(want, what):
+    r = _lib.last_gemm_route()
+    assert {f: r.get(f) for f in want} == want, (what, want, r)
+    return r
+
+
+def to16(ref64):
+    """float64 (exact in fp32) -> f16, one rounding."""
+    return ref64.float().half()

@@ -24,9 +24,10 @@ tile or tail bug.
    another f16 value) on every launch shape the suite forces.
 
 Out of scope, by design: the LN-fold routes (they contain rsqrt);
-conv3x3_up and the head ops (bilinear weights, sigmoid) -- conv3x3_up only at
-the source's own size, where every blend weight is 0, for its GELU site
-(test_gelu_upconv); the persistent conv,
+conv3x3_up and the head ops (bilinear weights, sigmoid: test_gpu_bilinear.py
+holds them to float64) -- conv3x3_up here only at the source's own size,
+where every blend weight is 0, for its GELU site (test_gelu_upconv, on a map
+of 8 rows: upconv_kernel takes an identity-size map of at most 12); the persistent conv,
 whose 1024-tile threshold makes its smallest shape the workload's own -- it is
 tied bit for bit to the per-tile kernel (test_conv_persist_bit_exact), which
 this file pins to float64.
@@ -35,7 +36,8 @@ Measured on an MI355X.  GELU, max(err - 0.5 ulp16) over the sweep (the bound
 allows 2.6e-5 + 2^-20 |ref|): 2.516e-5 at x = -3.0857 on the 64^2 tiles and
 the 128^2 BK 32 tiles, 2.512e-5 at x = -3.0916 on gemm256, 2.511e-5 at x =
 -3.0671 on the 128^2 BK 64 tiles, both panel kernels, the split-K store, the
-conv and both upsampling-conv kernels; every site equal to the 64^2-tile site.
+conv, conv3_kernel's upsampling form (route conv=conv3_up) and upconv_kernel's
+scalar gelu_erf (route conv=upconv); every site equal to the 64^2-tile site.
 erff (mde_op_linear32): 1.331e-3 of max(|ref|, 2^-14) at x = -5.5398.
 attention32's selection probe: at most 1.8e-7 relative.
 
@@ -59,51 +61,12 @@ import pytest
 import torch
 
 import exact_cases as X
-from gpu_util import close, conv_w, nhwc, op, pad_w, ptr, stream, vt_perm
+from gpu_util import assert_equal, assert_route, close, conv_w, nhwc, op, pad_w, ptr, stream, to16, vt_perm
 from monocular_depth_estimation_trt_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
-
-
-def ordinal16(t):
-    """f16 -> int32, monotone in the value (+0 and -0 both 0): differences are ulps."""
-    b = t.contiguous().view(torch.int16).int()
-    return torch.where(b < 0, -(b & 0x7FFF), b)
-
-
-def assert_equal(got, ref, what):
-    """torch.equal(got, ref) by value (zeros of either sign agree, NaN never
-    does); on failure the count, the bounding box and the largest difference."""
-    g = got.detach().cpu()
-    assert g.shape == ref.shape and g.dtype == ref.dtype, (what, g.shape, ref.shape, g.dtype, ref.dtype)
-    if torch.equal(g, ref):
-        return
-    g2, r2 = g.reshape(-1, g.shape[-1]), ref.reshape(-1, ref.shape[-1])
-    bad = g2 != r2
-    rows, cols = bad.any(1).nonzero().flatten(), bad.any(0).nonzero().flatten()
-    if g.dtype == torch.float16:
-        d = (ordinal16(g2) - ordinal16(r2)).abs()[bad]
-        worst = f"max {int(d.max())} f16 ulp"
-    else:
-        worst = f"max |d| {float((g2.double() - r2.double()).abs()[bad].nan_to_num(float('inf')).max()):.3e}"
-    i = int(bad.flatten().nonzero()[0])
-    raise AssertionError(
-        f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from float64, rows {int(rows[0])}..{int(rows[-1])} "
-        f"cols {int(cols[0])}..{int(cols[-1])} of {tuple(g2.shape)}, {worst}, {int(torch.isnan(g2).sum())} NaN; "
-        f"first [{i // g2.shape[1]}][{i % g2.shape[1]}] got {float(g2.flatten()[i])!r} ref {float(r2.flatten()[i])!r}")
-
-
-def assert_route(want, what):
-    r = _lib.last_gemm_route()
-    assert {f: r.get(f) for f in want} == want, (what, want, r)
-    return r
-
-
-def to16(ref64):
-    """float64 (exact in fp32) -> f16, one rounding."""
-    return ref64.float().half()
 
 
 def ln_partials_ref(xh):
@@ -456,7 +419,7 @@ def test_gelu_conv(gpu, gelu_table):
     out = torch.full((B, h, w, c), NAN, dtype=torch.float16, device=gpu)
     op("mde_op_conv3x3", ptr(x.to(gpu)), B, h, w, c, ptr(wp), wp.shape[1], c, 1, 0,
        ptr(X.GELU_BIAS[cls].float().to(gpu)), 2, None, None, ptr(out), stream())
-    assert_route(dict(kind="conv_direct"), "GELU conv")
+    assert_route(dict(kind="conv_direct", conv="conv3"), "GELU conv")
     idx = torch.arange(X.NSEQ).reshape(-1, c)
     cls = cls[None, :].expand_as(idx)
     check_gelu(out.cpu().reshape(-1, c), X.sweep_x(idx, cls), "conv3x3")
@@ -469,9 +432,15 @@ def test_gelu_upconv(gpu, gelu_table, upconv):
     conv3_kernel's tile_epilogue.h site): mde_op_conv3x3_up at the source's own
     size -- align_corners scale exactly 1, every blend weight exactly 0, so the
     upsampled map is the map -- with a centre-tap identity kernel, 32 -> 32 on
-    a 31 x 64 map.  The values ascend by bit pattern, so a pixel's right and
-    lower neighbours have its sign or are tiny: no f16 overflow in b - a."""
-    B, h, w, c = 1, 31, 64, 32
+    eight 8 x 31 maps.  upconv_kernel takes a map only when every 16-row tile
+    reads at most 12 source rows (conv.hip upconv_eligible); at ratio 1 that
+    is a map of at most 12 rows, and the route record says which kernel ran.
+    The values ascend by bit pattern and one image holds 7936
+    of them, so images 0..3 are the non-negative and 4..7 the negative
+    values: a pixel's right and lower neighbours (the b of a + (b - a) w)
+    have its sign, and b - a cannot overflow f16."""
+    B, h, w, c = X.GELU_UPCONV
+    assert B * h * w * c == X.NSEQ and (X.NSEQ // 2) % (h * w * c) == 0
     x = X.finite_f16().reshape(B, h, w, c)
     wt = torch.zeros(c, c, 3, 3)
     wt[torch.arange(c), torch.arange(c), 1, 1] = 1.0
@@ -481,7 +450,7 @@ def test_gelu_upconv(gpu, gelu_table, upconv):
     with _lib.tuning(upconv=upconv):
         op("mde_op_conv3x3_up", ptr(x.to(gpu)), B, h, w, c, h, w, ptr(wp), wp.shape[1], c,
            ptr(X.GELU_BIAS[cls].float().to(gpu)), 2, ptr(out), stream())
-    assert_route(dict(kind="conv_direct"), "GELU upconv")
+    assert_route(dict(kind="conv_direct", conv="upconv" if upconv else "conv3_up"), "GELU upconv")
     idx = torch.arange(X.NSEQ).reshape(-1, c)
     cls = cls[None, :].expand_as(idx)
     check_gelu(out.cpu().reshape(-1, c), X.sweep_x(idx, cls), f"conv3x3_up (upconv {upconv})")

@@ -696,6 +696,8 @@ def test_conv_persist_bit_exact(gpu, B, h, w, relu_in, act, nres, bias):
             op("mde_op_conv3x3", ptr(xg), B, h, w, 64, ptr(wp), wp.shape[1], 64, 1, relu_in, ptr(bg) if bias else None,
                act, ptr(rg[0]), ptr(rg[1]), ptr(out), stream())
         torch.cuda.synchronize()
+        r = _lib.last_gemm_route()
+        assert (r["kind"], r["conv"]) == ("conv_direct", "conv64p" if flag else "conv3"), (flag, r)
         got.append(out)
     close(nchw(got[1]), ref, 1e-2, 1e-2, f"persistent conv {B}x{h}x{w} relu_in={relu_in} nres={nres}")
     assert torch.equal(got[1], got[0]), "persistent conv (8 x 16 tiles) must equal the per-tile kernel bit for bit"
