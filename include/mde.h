@@ -140,6 +140,27 @@ int mde_tuning_get(const char* name, int* value);
  * takes the fields by name: later versions may add some.  MDE_ERR_ARG: null
  * buffer, or n too small (128 suffices). */
 int mde_debug_last_gemm_route(char* buf, size_t n);
+/* The same for the calling thread's last f16 attention launch
+ * (mde_op_attention, _ws, _cfg, and each attention layer of an enqueue; the
+ * fp32 op has the record below): what was launched after every
+ * fall-back of the launcher, e.g. "kernel=mfma32 nw=8 groups=4 split=1 tiles=0
+ * ring=2 qs=1 tail=0 nqb=22 nkt=22".  kernel: none (nothing launched yet, an
+ * empty problem, or a call rejected with MDE_ERR_ARG -- no other field then), mfma32 (the 32x32x16 kernel),
+ * mfma16 (the 16x16x32 kernel); nw waves per workgroup; groups key groups
+ * inside the workgroup (1: none -- also when a forced count exceeds the key
+ * tiles); split the key splits over the grid that were launched, with the
+ * combine kernel behind them (1: none -- also when the split collapsed or the
+ * workspace was too small) and tiles the key tiles of each; ring the K / V^T
+ * ring depth; qs the 32-query sub-tiles per wave; tail the "attn_tail" switch
+ * handed to the mfma16 kernel (0 for mfma32); nqb query blocks per (sequence,
+ * head); nkt 64-key tiles.  Fields by name, errors and n as above. */
+int mde_debug_last_attention_route(char* buf, size_t n);
+/* And for the fp32 attention (mde_op_attention32, the fp32 engines' attention
+ * layers): "kernel=fp32 key_groups=4 nqb=43" -- key_groups 4: four waves share
+ * one 32-query block and a quarter of the keys each (small grids); 1: four
+ * 32-query blocks per workgroup over all keys; nqb query blocks per
+ * (sequence, head) -- or "kernel=none" as above. */
+int mde_debug_last_attention32_route(char* buf, size_t n);
 
 /* ---- engine (replaces get_engine / ICudaEngine) ----------------------- */
 int mde_engine_load(const char* packed_path, int device, mde_engine** out);

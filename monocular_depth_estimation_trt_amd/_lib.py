@@ -62,6 +62,8 @@ PROTOTYPES = {
     "mde_tuning_set": [c_char_p, c_int],
     "mde_tuning_get": [c_char_p, P(c_int)],
     "mde_debug_last_gemm_route": [c_char_p, c_size_t],
+    "mde_debug_last_attention_route": [c_char_p, c_size_t],
+    "mde_debug_last_attention32_route": [c_char_p, c_size_t],
     "mde_engine_load": [c_char_p, c_int, P(c_void_p)],
     "mde_engine_load_memory": [c_void_p, c_size_t, c_int, P(c_void_p)],
     "mde_engine_destroy": [c_void_p],
@@ -352,6 +354,25 @@ def last_gemm_route() -> dict:
     call("mde_debug_last_gemm_route", buf, len(buf))
     fields = dict(f.split("=", 1) for f in buf.value.decode().split())
     return {k: v if k in ("kind", "conv") else int(v) for k, v in fields.items()}
+
+
+def last_attention_route() -> dict:
+    """What this thread's last f16 attention launch ran (include/mde.h
+    mde_debug_last_attention_route): {"kernel": "mfma32", "nw": 8, "groups": 4,
+    "split": 1, ...}, or {"kernel": "none"}."""
+    buf = C.create_string_buffer(256)
+    call("mde_debug_last_attention_route", buf, len(buf))
+    fields = dict(f.split("=", 1) for f in buf.value.decode().split())
+    return {k: v if k == "kernel" else int(v) for k, v in fields.items()}
+
+
+def last_attention32_route() -> dict:
+    """Which shape this thread's last fp32 attention launch took (include/mde.h
+    mde_debug_last_attention32_route): {"kernel": "fp32", "key_groups": 4, "nqb": 43}."""
+    buf = C.create_string_buffer(256)
+    call("mde_debug_last_attention32_route", buf, len(buf))
+    fields = dict(f.split("=", 1) for f in buf.value.decode().split())
+    return {k: v if k == "kernel" else int(v) for k, v in fields.items()}
 
 
 def exported_symbols():

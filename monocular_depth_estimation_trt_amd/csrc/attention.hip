@@ -840,31 +840,32 @@ __global__ void __launch_bounds__(256) attn_combine_kernel(SplitWs ws, int S, in
   *reinterpret_cast<f16x8*>(o + ((size_t)b * T + qi) * ldo + h * 64 + 8 * d8) = v;
 }
 
+// The launchers below launch what an AttnRoute (mde_ops.h) says: grid from
+// r.nqb, the split from r.split / r.tiles.  No policy here.
 template <int NW, int R, int QS = 1>
 hipError_t run_attn(const h16* q, const h16* k, const h16* vt, h16* o, int B, int H, int T, int Tpad, int ldo,
-                    float* ws, size_t ws_bytes, int split, hipStream_t st) {
+                    float* ws, const AttnRoute& r, hipStream_t st) {
   constexpr int BQ = QW * NW * QS;
-  const int nqb = (T + BQ - 1) / BQ, nkt = (T + KT - 1) / KT;
+  const int nqb = r.nqb;
   const auto cq = reinterpret_cast<const f16*>(q);
   const auto ck = reinterpret_cast<const f16*>(k);
   const auto cv = reinterpret_cast<const f16*>(vt);
   const auto co = reinterpret_cast<f16*>(o);
-  if (QS == 1 && split > 1 && ws) {
-    SplitWs w;
-    w.Tq = nqb * BQ;
-    w.tiles = (nkt + split - 1) / split;
-    const int S = (nkt + w.tiles - 1) / w.tiles;  // every split non-empty
-    const size_t rows = (size_t)S * B * H * w.Tq;
-    if (S > 1 && rows * 66 * sizeof(float) <= ws_bytes) {
+  if constexpr (QS == 1) {
+    if (r.split > 1) {
+      SplitWs w;
+      w.Tq = nqb * BQ;
+      w.tiles = r.tiles;
+      const size_t rows = (size_t)r.split * B * H * w.Tq;
       w.o = ws;
       w.ml = ws + rows * 64;
-      hipLaunchKernelGGL((attn_fwd_kernel<NW, true, R, 1>), dim3(nqb, B * H, S), dim3(NW * 64), 0, st, cq, ck, cv, co, H, T,
-                         Tpad, ldo, w);
+      hipLaunchKernelGGL((attn_fwd_kernel<NW, true, R, 1>), dim3(nqb, B * H, r.split), dim3(NW * 64), 0, st, cq, ck, cv,
+                         co, H, T, Tpad, ldo, w);
       const hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
       const long long n = (long long)B * H * T * 8;
-      hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, S, B * H, H, T,
-                         ldo, co);
+      hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, r.split, B * H, H,
+                         T, ldo, co);
       return hipGetLastError();
     }
   }
@@ -876,10 +877,8 @@ hipError_t run_attn(const h16* q, const h16* k, const h16* vt, h16* o, int B, in
 // NS key groups of NW / NS query waves in each workgroup (in-workgroup split-KV)
 template <int NW, int NS>
 hipError_t run_attn_grp(const h16* q, const h16* k, const h16* vt, h16* o, int B, int H, int T, int Tpad, int ldo,
-                        hipStream_t st) {
-  constexpr int BQ = QW * (NW / NS);
-  const int nqb = (T + BQ - 1) / BQ;
-  hipLaunchKernelGGL((attn_fwd_kernel<NW, false, 2, 1, NS>), dim3(nqb, B * H), dim3(NW * 64), 0, st,
+                        const AttnRoute& r, hipStream_t st) {
+  hipLaunchKernelGGL((attn_fwd_kernel<NW, false, 2, 1, NS>), dim3(r.nqb, B * H), dim3(NW * 64), 0, st,
                      reinterpret_cast<const f16*>(q), reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(vt),
                      reinterpret_cast<f16*>(o), H, T, Tpad, ldo, SplitWs{});
   return hipGetLastError();
@@ -887,28 +886,16 @@ hipError_t run_attn_grp(const h16* q, const h16* k, const h16* vt, h16* o, int B
 
 template <int NW, int NS = 1>
 hipError_t run_attn16(const h16* q, const h16* k, const h16* vt, h16* o, int B, int H, int T, int Tpad, int ldo,
-                      hipStream_t st) {
-  constexpr int BQ = QW * (NW / NS);
-  const int nqb = (T + BQ - 1) / BQ;
-  hipLaunchKernelGGL((attn16_fwd_kernel<NW, NS>), dim3(nqb, B * H), dim3(NW * 64), 0, st, reinterpret_cast<const f16*>(q),
+                      const AttnRoute& r, hipStream_t st) {
+  hipLaunchKernelGGL((attn16_fwd_kernel<NW, NS>), dim3(r.nqb, B * H), dim3(NW * 64), 0, st, reinterpret_cast<const f16*>(q),
                      reinterpret_cast<const f16*>(k), reinterpret_cast<const f16*>(vt), reinterpret_cast<f16*>(o), H, T,
-                     Tpad, ldo, knob(KNOB_ATTN_TAIL));
+                     Tpad, ldo, r.tail);
   return hipGetLastError();
 }
 
-}  // namespace
-
-size_t attention_split_ws_bytes(int B, int H, int T) {
-  // the largest split the launcher picks: 8 ways over 128-query workgroups
-  const size_t tq = (size_t)(T + 127) / 128 * 128;
-  return (size_t)8 * B * H * tq * 66 * sizeof(float);
-}
-
-hipError_t launch_attention(const h16* q, const h16* k, const h16* vt, h16* o, int B, int H, int T, int Tpad,
-                            int ldo, hipStream_t st, float* ws, size_t ws_bytes, const char* cfg) {
-  if (B <= 0 || T <= 0) return hipSuccess;
-  // the 16-B output stores need ldo % 8 == 0 (and a 16-B aligned o)
-  if (Tpad % KT || Tpad < ((T + KT - 1) / KT) * KT || (ldo & 7) || ((uintptr_t)o & 15)) return hipErrorInvalidValue;
+// The one decision of what launch_attention launches for (B, H, T) with this
+// workspace and cfg (policy and every fall-back; no device call).  B, T > 0.
+AttnRoute attention_route(int B, int H, int T, const float* ws, size_t ws_bytes, const char* cfg) {
   const int nkt = (T + KT - 1) / KT;
   // cfg = <waves>[s<split>][g<groups>][r<ring>][q2] ("8", "4", "4s8", "8r3", ...):
   // a forced launch shape (mde_op_attention_cfg: tests, tuning)
@@ -958,33 +945,107 @@ hipError_t launch_attention(const h16* q, const h16* k, const h16* vt, h16* o, i
   // 32x32x16 one at batch 1: ViT-L 17.4-17.9 vs 16.9-17.4 us, ViT-S 12.4-12.7
   // vs 12.1-12.4, gpurun_out r6s24 -- the switch covers the unsplit shape only)
   if (!forced && nw == 8 && groups == 1 && split <= 1) m16 = knob(KNOB_ATTN16);
-  if (m16 && groups > 1 && nkt >= groups && nw == 8 && split <= 1 && !qs2) {
-    if (groups == 2) return run_attn16<8, 2>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (groups == 4) return run_attn16<8, 4>(q, k, vt, o, B, H, T, Tpad, ldo, st);
+
+  AttnRoute r;
+  r.nkt = nkt;
+  // key groups need a key tile each; a count that does not fit falls back to
+  // the ungrouped kernels below
+  const bool fits = groups > 1 && nkt >= groups;
+  const bool grp32 = fits && ((nw == 4 && (groups == 2 || groups == 4)) || (nw == 8 && (groups == 2 || groups == 4)) ||
+                              (nw == 12 && groups == 3) || (nw == 6 && groups == 2) || (nw == 16 && groups == 4));
+  if (m16 && split <= 1 && !qs2 &&
+      ((fits && nw == 8 && (groups == 2 || groups == 4)) || (groups == 1 && (nw == 8 || nw == 4)))) {
+    r.kernel = ATTN_K_MFMA16;
+    r.nw = nw;
+    r.groups = groups;
+    r.tail = knob(KNOB_ATTN_TAIL);
+  } else if (grp32) {
+    r.kernel = ATTN_K_MFMA32;
+    r.nw = nw;
+    r.groups = groups;
+  } else {
+    r.kernel = ATTN_K_MFMA32;
+    r.groups = 1;
+    if ((nw == 8 || nw == 4) && qs2 && split <= 1) {
+      r.nw = nw;
+      r.qs = 2;
+    } else {
+      r.nw = nw == 8 ? 8 : 4;
+      r.ring = ring == 3 || ring == 4 ? ring : 2;
+      if (split > 1 && ws) {
+        // every split non-empty; one that collapses to 1, or whose partials
+        // do not fit the workspace, runs unsplit
+        const int tiles = (nkt + split - 1) / split, S = (nkt + tiles - 1) / tiles;
+        const size_t tq = (size_t)((T + QW * r.nw - 1) / (QW * r.nw)) * (QW * r.nw);
+        if (S > 1 && (size_t)S * B * H * tq * 66 * sizeof(float) <= ws_bytes) {
+          r.split = S;
+          r.tiles = tiles;
+        }
+      }
+    }
   }
-  if (m16 && groups == 1 && split <= 1 && !qs2) {
-    if (nw == 8) return run_attn16<8>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (nw == 4) return run_attn16<4>(q, k, vt, o, B, H, T, Tpad, ldo, st);
+  const int bq = QW * (r.nw / r.groups) * r.qs;
+  r.nqb = (T + bq - 1) / bq;
+  return r;
+}
+
+thread_local AttnRoute t_last_attn_route;
+
+}  // namespace
+
+const AttnRoute& attention_last_route() { return t_last_attn_route; }
+
+size_t attention_split_ws_bytes(int B, int H, int T) {
+  // the largest split the launcher picks: 8 ways over 128-query workgroups
+  const size_t tq = (size_t)(T + 127) / 128 * 128;
+  return (size_t)8 * B * H * tq * 66 * sizeof(float);
+}
+
+hipError_t launch_attention(const h16* q, const h16* k, const h16* vt, h16* o, int B, int H, int T, int Tpad,
+                            int ldo, hipStream_t st, float* ws, size_t ws_bytes, const char* cfg) {
+  if (B <= 0 || T <= 0) {
+    t_last_attn_route = AttnRoute{};
+    return hipSuccess;
   }
-  if (groups > 1 && nkt >= groups) {
-    if (nw == 4 && groups == 2) return run_attn_grp<4, 2>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (nw == 4 && groups == 4) return run_attn_grp<4, 4>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (nw == 8 && groups == 2) return run_attn_grp<8, 2>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (nw == 8 && groups == 4) return run_attn_grp<8, 4>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (nw == 12 && groups == 3) return run_attn_grp<12, 3>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (nw == 6 && groups == 2) return run_attn_grp<6, 2>(q, k, vt, o, B, H, T, Tpad, ldo, st);
-    if (nw == 16 && groups == 4) return run_attn_grp<16, 4>(q, k, vt, o, B, H, T, Tpad, ldo, st);
+  // the 16-B output stores need ldo % 8 == 0 (and a 16-B aligned o)
+  if (Tpad % KT || Tpad < ((T + KT - 1) / KT) * KT || (ldo & 7) || ((uintptr_t)o & 15)) {
+    t_last_attn_route = AttnRoute{};  // nothing launched: the record must not show the launch before
+    return hipErrorInvalidValue;
   }
-  if (nw == 8 && qs2 && split <= 1) return run_attn<8, 2, 2>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, 1, st);
-  if (nw == 4 && qs2 && split <= 1) return run_attn<4, 2, 2>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, 1, st);
-  if (nw == 8) {
-    if (ring == 4) return run_attn<8, 4>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, split, st);
-    if (ring == 3) return run_attn<8, 3>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, split, st);
-    return run_attn<8, 2>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, split, st);
+  const AttnRoute r = attention_route(B, H, T, ws, ws_bytes, cfg);
+  t_last_attn_route = r;
+#define ATTN_ARGS q, k, vt, o, B, H, T, Tpad, ldo
+  if (r.kernel == ATTN_K_MFMA16) {
+    if (r.nw == 8 && r.groups == 2) return run_attn16<8, 2>(ATTN_ARGS, r, st);
+    if (r.nw == 8 && r.groups == 4) return run_attn16<8, 4>(ATTN_ARGS, r, st);
+    if (r.nw == 8 && r.groups == 1) return run_attn16<8>(ATTN_ARGS, r, st);
+    if (r.nw == 4 && r.groups == 1) return run_attn16<4>(ATTN_ARGS, r, st);
+    return hipErrorInvalidValue;  // a route without an instantiation: attention_route and this list disagree
   }
-  if (ring == 4) return run_attn<4, 4>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, split, st);
-  if (ring == 3) return run_attn<4, 3>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, split, st);
-  return run_attn<4, 2>(q, k, vt, o, B, H, T, Tpad, ldo, ws, ws_bytes, split, st);
+  if (r.groups > 1) {
+    if (r.nw == 4 && r.groups == 2) return run_attn_grp<4, 2>(ATTN_ARGS, r, st);
+    if (r.nw == 4 && r.groups == 4) return run_attn_grp<4, 4>(ATTN_ARGS, r, st);
+    if (r.nw == 8 && r.groups == 2) return run_attn_grp<8, 2>(ATTN_ARGS, r, st);
+    if (r.nw == 8 && r.groups == 4) return run_attn_grp<8, 4>(ATTN_ARGS, r, st);
+    if (r.nw == 12 && r.groups == 3) return run_attn_grp<12, 3>(ATTN_ARGS, r, st);
+    if (r.nw == 6 && r.groups == 2) return run_attn_grp<6, 2>(ATTN_ARGS, r, st);
+    if (r.nw == 16 && r.groups == 4) return run_attn_grp<16, 4>(ATTN_ARGS, r, st);
+    return hipErrorInvalidValue;
+  }
+  if (r.qs == 2 && r.nw == 8) return run_attn<8, 2, 2>(ATTN_ARGS, ws, r, st);
+  if (r.qs == 2 && r.nw == 4) return run_attn<4, 2, 2>(ATTN_ARGS, ws, r, st);
+  if (r.qs == 1 && r.nw == 8) {
+    if (r.ring == 4) return run_attn<8, 4>(ATTN_ARGS, ws, r, st);
+    if (r.ring == 3) return run_attn<8, 3>(ATTN_ARGS, ws, r, st);
+    if (r.ring == 2) return run_attn<8, 2>(ATTN_ARGS, ws, r, st);
+  }
+  if (r.qs == 1 && r.nw == 4) {
+    if (r.ring == 4) return run_attn<4, 4>(ATTN_ARGS, ws, r, st);
+    if (r.ring == 3) return run_attn<4, 3>(ATTN_ARGS, ws, r, st);
+    if (r.ring == 2) return run_attn<4, 2>(ATTN_ARGS, ws, r, st);
+  }
+  return hipErrorInvalidValue;
+#undef ATTN_ARGS
 }
 
 }  // namespace mde

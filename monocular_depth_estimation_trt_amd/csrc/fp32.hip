@@ -570,21 +570,36 @@ hipError_t launch_gemm32(const Gemm32Params& p, hipStream_t st) {
   return run32<64, 64>(p, st);
 }
 
+namespace {
+
+// four 32-query blocks over all keys once 128-query workgroups number 512;
+// below that (batch 1) four key groups on one 32-query block
+Attn32Route attention32_route(int B, int H, int T) {
+  Attn32Route r;
+  r.key_groups = (long long)B * H * ((T + 127) / 128) >= 512 ? 1 : 4;
+  const int bq = 32 * (4 / r.key_groups);
+  r.nqb = (T + bq - 1) / bq;
+  return r;
+}
+
+thread_local Attn32Route t_last_attn32_route;
+
+}  // namespace
+
+const Attn32Route& attention32_last_route() { return t_last_attn32_route; }
+
 hipError_t launch_attention32(const float* q, const float* k, const float* v, float* o, int B, int H, int T,
                               int Tpad, int ldo, hipStream_t st) {
+  t_last_attn32_route = Attn32Route{};
   if (B <= 0 || T <= 0) return hipSuccess;
   if (!q || !k || !v || !o || Tpad < T || (ldo & 3) || ldo < H * 64 || ((uintptr_t)o & 15)) return hipErrorInvalidValue;
-  const long long bh = (long long)B * H;
-  const long long wg128 = bh * ((T + 127) / 128);
-  if (wg128 >= 512) {
-    const int nqb = (T + 127) / 128;
-    hipLaunchKernelGGL((attn32_kernel<1>), dim3((unsigned)(bh * nqb)), dim3(256), 0, st, q, k, v, o, H, T, Tpad, ldo,
-                       nqb);
-  } else {
-    const int nqb = (T + 31) / 32;
-    hipLaunchKernelGGL((attn32_kernel<4>), dim3((unsigned)(bh * nqb)), dim3(256), 0, st, q, k, v, o, H, T, Tpad, ldo,
-                       nqb);
-  }
+  const Attn32Route r = attention32_route(B, H, T);
+  t_last_attn32_route = r;
+  const dim3 grid((unsigned)((long long)B * H * r.nqb));
+  if (r.key_groups == 1)
+    hipLaunchKernelGGL((attn32_kernel<1>), grid, dim3(256), 0, st, q, k, v, o, H, T, Tpad, ldo, r.nqb);
+  else
+    hipLaunchKernelGGL((attn32_kernel<4>), grid, dim3(256), 0, st, q, k, v, o, H, T, Tpad, ldo, r.nqb);
   return hipGetLastError();
 }
 

@@ -152,6 +152,14 @@ hipError_t launch_head32(const float* hid, const float* w2, float b2, int M, int
 // [B*H][Tpad][64] rows -> o fp32 [B*T][ldo], head h in columns 64h .. 64h+63
 hipError_t launch_attention32(const float* q, const float* k, const float* v, float* o, int B, int H, int T,
                               int Tpad, int ldo, hipStream_t st);
+// which of its two shapes the calling thread's last launch_attention32 launched
+// (fp32.hip decides once and launches from it; mde_debug_last_attention32_route)
+struct Attn32Route {
+  int key_groups = 0;  // 4: attn32_kernel<4>, one 32-query block per workgroup; 1: attn32_kernel<1>,
+                       // four blocks over all keys; 0: nothing launched (yet, empty or rejected)
+  int nqb = 0;         // query blocks per (sequence, head)
+};
+const Attn32Route& attention32_last_route();
 
 
 // x32[m*ldo+n] += ls[n] * (sum_{s<S} P[s][m][n] + bias[n]), slices summed in
@@ -212,6 +220,30 @@ hipError_t launch_attention(const h16* q, const h16* k, const h16* vt, h16* o, i
                             int Tpad, int ldo, hipStream_t st, float* ws = nullptr, size_t ws_bytes = 0,
                             const char* cfg = nullptr);
 size_t attention_split_ws_bytes(int B, int H, int T);
+// What launch_attention launches for a problem (attention.hip attention_route
+// decides: policy or cfg, and every fall-back -- key groups that do not fit
+// the key tiles, a split that collapses or whose workspace is too small;
+// launch_attention launches from the decision and keeps a copy per thread for
+// the tests, mde_debug_last_attention_route in include/mde.h).
+// A rejected call (hipErrorInvalidValue) resets the record like an empty one.
+enum AttnKernel : int {
+  ATTN_K_NONE = 0,  // nothing launched yet on this thread, or an empty problem
+  ATTN_K_MFMA32,    // attn_fwd_kernel (v_mfma_f32_32x32x16_f16)
+  ATTN_K_MFMA16     // attn16_fwd_kernel (v_mfma_f32_16x16x32_f16)
+};
+struct AttnRoute {
+  int kernel = ATTN_K_NONE;
+  int nw = 0;      // waves per workgroup
+  int groups = 1;  // key groups inside the workgroup (1 = none)
+  int split = 1;   // key splits over gridDim.z actually launched (1 = none: no combine launch)
+  int tiles = 0;   // key tiles per split (split > 1)
+  int ring = 2;    // K / V^T ring depth
+  int qs = 1;      // 32-query sub-tiles per wave
+  int tail = 0;    // MFMA16: the attn_tail switch handed to the kernel; else 0
+  int nqb = 0;     // query blocks per (sequence, head): gridDim.x
+  int nkt = 0;     // 64-key tiles
+};
+const AttnRoute& attention_last_route();
 
 // x (fp32) or xh (f16) residual rows -> LayerNorm -> f16 y
 hipError_t launch_layernorm(const float* x, h16* y, const float* g, const float* b, int rows, int D,

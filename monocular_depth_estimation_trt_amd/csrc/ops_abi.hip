@@ -42,6 +42,29 @@ int mde_debug_last_gemm_route(char* buf, size_t n) {
   return MDE_OK;
 }
 
+int mde_debug_last_attention_route(char* buf, size_t n) {
+  static const char* const kKernel[] = {"none", "mfma32", "mfma16"};
+  const AttnRoute& r = attention_last_route();
+  if (!buf) return fail(MDE_ERR_ARG, "mde_debug_last_attention_route: null buffer");
+  int len;
+  if (r.kernel == ATTN_K_MFMA32 || r.kernel == ATTN_K_MFMA16)
+    len = snprintf(buf, n, "kernel=%s nw=%d groups=%d split=%d tiles=%d ring=%d qs=%d tail=%d nqb=%d nkt=%d",
+                   kKernel[r.kernel], r.nw, r.groups, r.split, r.tiles, r.ring, r.qs, r.tail, r.nqb, r.nkt);
+  else
+    len = snprintf(buf, n, "kernel=%s", kKernel[0]);
+  if (len < 0 || (size_t)len >= n) return fail(MDE_ERR_ARG, "mde_debug_last_attention_route: buffer too small");
+  return MDE_OK;
+}
+
+int mde_debug_last_attention32_route(char* buf, size_t n) {
+  const Attn32Route& r = attention32_last_route();
+  if (!buf) return fail(MDE_ERR_ARG, "mde_debug_last_attention32_route: null buffer");
+  const int len = r.key_groups ? snprintf(buf, n, "kernel=fp32 key_groups=%d nqb=%d", r.key_groups, r.nqb)
+                               : snprintf(buf, n, "kernel=none");
+  if (len < 0 || (size_t)len >= n) return fail(MDE_ERR_ARG, "mde_debug_last_attention32_route: buffer too small");
+  return MDE_OK;
+}
+
 int mde_op_patch_prep_u8(const unsigned char* img, int batch, int h, int w, float scale, const float* mean3,
                          const float* std3, void* patches, void* st) {
   if (!img || !mean3 || !std3 || !patches || batch < 1 || h % 14 || w % 14 || h < 14 || w < 14)

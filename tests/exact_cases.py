@@ -30,6 +30,7 @@ from __future__ import annotations
 
 import functools
 import math
+import re
 import zlib
 
 import numpy as np
@@ -330,6 +331,61 @@ def gelu_erf_emulated(x):
 
 ATTN_SHAPES = [(1, 2, 1370), (2, 3, 300), (2, 3, 129), (3, 1, 65)]   # (B, H, T); (1, 1, 1) for the uniform probe
 ATTN_CFGS = "4g2 8g2 4g4 8g4 12g3 16g4 6g2 8g2m 8g4m 8 4 8q2 4q2 8r3 4r4 4s2 4s3 8m 4m".split()
+# (name, cfg or None for the policy, "attn_tail" or None for its default): every launch shape the suite forces
+ATTN_LAUNCHES = ([("policy", None, None), ("ws", None, None)] + [(c, c, None) for c in ATTN_CFGS]
+                 + [(f"8m_tail{t}", "8m", t) for t in (0, 1, 2)])
+
+
+# What mde_op_attention / _ws launch at the shapes above, from the promises of
+# launch_attention's comment block: 256-query workgroups of 8 waves once
+# ceil(T / 256) B H >= 512, else 128-query groups of 4 waves; below 256 such
+# groups the keys split while each split keeps 7 key tiles (T = 1370: 22
+# tiles, 3 splits; T <= 300: under 14 tiles, none); a 3-way split whose
+# 64-query grid fits the CUs (44 <= 256) runs as four key groups in one
+# 8-wave workgroup.  The "attn16" switch covers the unsplit 8-wave shape only.
+ATTN_POLICY = {
+    (1, 2, 1370): dict(kernel="mfma32", nw=8, groups=4, split=1, ring=2, qs=1, tail=0, nqb=22, nkt=22),
+    (2, 3, 300): dict(kernel="mfma32", nw=4, groups=1, split=1, ring=2, qs=1, tail=0, nqb=3, nkt=5),
+    (2, 3, 129): dict(kernel="mfma32", nw=4, groups=1, split=1, ring=2, qs=1, tail=0, nqb=2, nkt=3),
+    (3, 1, 65): dict(kernel="mfma32", nw=4, groups=1, split=1, ring=2, qs=1, tail=0, nqb=1, nkt=2),
+    (1, 1, 1): dict(kernel="mfma32", nw=4, groups=1, split=1, ring=2, qs=1, tail=0, nqb=1, nkt=1),
+}
+ATTN_TAIL_DEFAULT = 2   # the library's "attn_tail" (include/mde.h)
+
+
+def attention_route_expected(cfg, tail, B, H, T):
+    """What _lib.last_attention_route() must show after a launch of cfg (None:
+    the policy) at (B, H, T), by the contract of the cfg string (mde.h
+    mde_op_attention_cfg, mde_ops.h): "<waves>[s<split>][g<groups>][r<ring>]
+    [q2][m]".
+      g<n>: n key groups of waves / n query waves, each at least one 64-key
+        tile -- with fewer tiles than groups the ungrouped 32x32x16 kernel
+        runs instead (8 waves for "8...", else 4), "m" or not.
+      m: the 16x16x32 kernel, handed the "attn_tail" switch.
+      s<n>: ceil(tiles / n) key tiles per split, hence S = ceil(tiles / that)
+        non-empty splits (the workspace of mde_op_attention_ws_bytes holds 8);
+        S = 1 launches unsplit, without the combine kernel.
+      r<n>: ring depth 3 or 4 (else 2); q2: two 32-query sub-tiles per wave.
+    nqb = ceil(T / (32 x query waves x sub-tiles))."""
+    if cfg is None:
+        return dict(ATTN_POLICY[(B, H, T)])
+    nkt = -(-T // 64)
+    f = re.fullmatch(r"(\d+)(?:s(\d+))?(?:g(\d+))?(?:r(\d+))?(q2)?(m)?", cfg)
+    assert f, cfg
+    nw, split, groups, ring = int(f[1]), int(f[2] or 1), int(f[3] or 1), int(f[4] or 2)
+    qs, m16 = 2 if f[5] else 1, bool(f[6])
+    want = dict(kernel="mfma16" if m16 else "mfma32", nw=nw, groups=groups, split=1, ring=ring, qs=qs, tail=0, nkt=nkt)
+    if groups > 1 and nkt < groups:    # the fallback: ungrouped, 32x32x16
+        want.update(kernel="mfma32", nw=8 if nw == 8 else 4, groups=1)
+    elif m16:
+        want["tail"] = ATTN_TAIL_DEFAULT if tail is None else tail
+    if split > 1:
+        per = -(-nkt // split)
+        want["split"] = -(-nkt // per)
+        if want["split"] > 1:
+            want["tiles"] = per
+    want["nqb"] = -(-T // (32 * (want["nw"] // want["groups"]) * qs))
+    return want
 
 
 def coprime_mult(T):

@@ -129,6 +129,38 @@ def assert_route(want, what):
     return r
 
 
+def assert_attn_route(want, what):
+    """The fields of _lib.last_attention_route() named in want."""
+    r = _lib.last_attention_route()
+    assert {f: r.get(f) for f in want} == want, (what, want, r)
+    return r
+
+
+def run_attention(gpu, launch, cfg, tail, q, k, v, B, H, T):
+    """q, k, v [B H][T][64] f16 -> o [B T][H 64]: V^T through vt_perm, the
+    pad of q, k and vt zero (the kernel's contract), o prefilled with NaN.
+    launch: "policy" (mde_op_attention), "ws" (mde_op_attention_ws) or a name
+    for cfg through mde_op_attention_cfg, with "attn_tail" = tail if given."""
+    Tp = -(-T // 64) * 64
+    qg = torch.zeros(B * H, Tp, 64, dtype=torch.float16, device=gpu)
+    kg = torch.zeros_like(qg)
+    vtg = torch.zeros(B * H, 64, Tp, dtype=torch.float16, device=gpu)
+    qg[:, :T], kg[:, :T] = q.to(gpu), k.to(gpu)
+    vtg[:, :, vt_perm(T).to(gpu)] = v.transpose(1, 2).to(gpu)
+    o = torch.full((B * T, H * 64), float("nan"), dtype=torch.float16, device=gpu)
+    nbytes = _lib.lib().mde_op_attention_ws_bytes(B, H, T)
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=gpu)
+    if launch == "policy":
+        op("mde_op_attention", ptr(qg), ptr(kg), ptr(vtg), ptr(o), B, H, T, Tp, H * 64, stream())
+    elif launch == "ws":
+        op("mde_op_attention_ws", ptr(qg), ptr(kg), ptr(vtg), ptr(o), B, H, T, Tp, H * 64, ptr(ws), nbytes, stream())
+    else:
+        with _lib.tuning(**({"attn_tail": tail} if tail is not None else {})):
+            op("mde_op_attention_cfg", ptr(qg), ptr(kg), ptr(vtg), ptr(o), B, H, T, Tp, H * 64, cfg.encode(), ptr(ws),
+               nbytes, stream())
+    return o
+
+
 def to16(ref64):
     """float64 (exact in fp32) -> f16, one rounding."""
     return ref64.float().half()

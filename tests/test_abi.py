@@ -109,6 +109,27 @@ def test_last_gemm_route_before_any_launch(lib_path):
     assert got == {"route": {"kind": "none"}, "rc": (1, 1)}, got
 
 
+def test_last_attention_route_before_any_launch(lib_path):
+    """mde_debug_last_attention_route on a new thread (the record is per
+    thread): no launch yet, and the same buffer checks."""
+    import threading
+    from monocular_depth_estimation_trt_amd import _lib
+    got = {}
+
+    def fresh_thread():
+        got["route"] = _lib.last_attention_route()
+        got["rc"] = (_lib.lib().mde_debug_last_attention_route(ctypes.create_string_buffer(4), 4),
+                     _lib.lib().mde_debug_last_attention_route(None, 0))
+        got["route32"] = _lib.last_attention32_route()
+        got["rc32"] = (_lib.lib().mde_debug_last_attention32_route(ctypes.create_string_buffer(4), 4),
+                       _lib.lib().mde_debug_last_attention32_route(None, 0))
+
+    t = threading.Thread(target=fresh_thread)
+    t.start()
+    t.join()
+    assert got == {"route": {"kernel": "none"}, "rc": (1, 1), "route32": {"kernel": "none"}, "rc32": (1, 1)}, got
+
+
 def _run_py(code, env=None):
     import subprocess
     import sys

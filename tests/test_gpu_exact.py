@@ -13,15 +13,18 @@ tile or tail bug.
 
 1. Linear / conv families, one case per route of launch_gemm
    (test_linear_strided's shapes, the smallest that reach each), every case
-   asserting the route it took.  The exact-fp32 kernels (fp32.hip) and the
-   attention launcher keep no route record: those cases assert none.
+   asserting the route it took.  The exact-fp32 kernels (fp32.hip) keep no
+   route record: those cases assert none.
 2. GELU: every finite f16 value through every epilogue that has one, against
    the float64 erf form at 0.5 ulp16 + 2.6e-5 (the bound mde_device.h
    documents) + 2^-20 |ref| (v_exp_f32, v_rcp_f32), and every site equal to
    the 64^2-tile site for the same (a, b).
 3. Attention: a selection probe (the output row is one V row) and a uniform
    probe (the output is V's constant column; one leaked pad key moves it to
-   another f16 value) on every launch shape the suite forces.
+   another f16 value) on every launch shape the suite forces, each asserting
+   what the launcher's record (mde_debug_last_attention_route) says ran --
+   a forced shape that cannot run at a size (four key groups over three key
+   tiles, a split that collapses) asserts its documented fallback.
 
 Out of scope, by design: the LN-fold routes (they contain rsqrt);
 conv3x3_up and the head ops (bilinear weights, sigmoid: test_gpu_bilinear.py
@@ -61,7 +64,8 @@ import pytest
 import torch
 
 import exact_cases as X
-from gpu_util import assert_equal, assert_route, close, conv_w, nhwc, op, pad_w, ptr, stream, to16, vt_perm
+from gpu_util import (assert_attn_route, assert_equal, assert_route, close, conv_w, nhwc, op, pad_w, ptr,
+                      run_attention, stream, to16, vt_perm)
 from monocular_depth_estimation_trt_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -485,31 +489,7 @@ def test_gelu_linear32(gpu):
 
 # ---- 3. attention: selection and uniform probes on every launch shape ------------
 
-LAUNCHES = ([("policy", None, None), ("ws", None, None)] + [(c, c, None) for c in X.ATTN_CFGS]
-            + [(f"8m_tail{t}", "8m", t) for t in (0, 1, 2)])
-
-
-def run_attention(gpu, launch, cfg, tail, q, k, v, B, H, T):
-    """q, k, v [B H][T][64] f16 -> o [B T][H 64]: V^T through vt_perm, the
-    pad of q, k and vt zero (the kernel's contract), o prefilled with NaN."""
-    Tp = -(-T // 64) * 64
-    qg = torch.zeros(B * H, Tp, 64, dtype=torch.float16, device=gpu)
-    kg = torch.zeros_like(qg)
-    vtg = torch.zeros(B * H, 64, Tp, dtype=torch.float16, device=gpu)
-    qg[:, :T], kg[:, :T] = q.to(gpu), k.to(gpu)
-    vtg[:, :, vt_perm(T).to(gpu)] = v.transpose(1, 2).to(gpu)
-    o = torch.full((B * T, H * 64), NAN, dtype=torch.float16, device=gpu)
-    nbytes = _lib.lib().mde_op_attention_ws_bytes(B, H, T)
-    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=gpu)
-    if launch == "policy":
-        op("mde_op_attention", ptr(qg), ptr(kg), ptr(vtg), ptr(o), B, H, T, Tp, H * 64, stream())
-    elif launch == "ws":
-        op("mde_op_attention_ws", ptr(qg), ptr(kg), ptr(vtg), ptr(o), B, H, T, Tp, H * 64, ptr(ws), nbytes, stream())
-    else:
-        with _lib.tuning(**({"attn_tail": tail} if tail is not None else {})):
-            op("mde_op_attention_cfg", ptr(qg), ptr(kg), ptr(vtg), ptr(o), B, H, T, Tp, H * 64, cfg.encode(), ptr(ws),
-               nbytes, stream())
-    return o
+LAUNCHES = X.ATTN_LAUNCHES
 
 
 @functools.lru_cache(maxsize=None)
@@ -529,6 +509,7 @@ def test_attention_selection(gpu, launch, cfg, tail, B, H, T):
     for inverse in (0, 1):
         q, k, v, exp = selection(B, H, T, inverse)
         o = run_attention(gpu, launch, cfg, tail, q, k, v, B, H, T)
+        assert_attn_route(X.attention_route_expected(cfg, tail, B, H, T), f"attention {launch} B{B} H{H} T{T}")
         assert_equal(o, exp, f"attention {launch} B{B} H{H} T{T} selection (inverse {inverse})")
 
 
@@ -540,6 +521,7 @@ def test_attention_uniform(gpu, launch, cfg, tail, B, H, T):
     the row by T / (T + 1) -- more than half an f16 ulp for every T here."""
     q, k, v, exp = X.uniform_case(B, H, T)
     o = run_attention(gpu, launch, cfg, tail, q, k, v, B, H, T)
+    assert_attn_route(X.attention_route_expected(cfg, tail, B, H, T), f"attention {launch} B{B} H{H} T{T}")
     assert_equal(o, exp, f"attention {launch} B{B} H{H} T{T} uniform")
 
 
